@@ -13,22 +13,27 @@ Workloads (`--workload`, default `auto`):
               buffer; a step = fused residual+Jacobian of the 8 members + the weighted infidelity / regulariser objective
               and its gradient + the merit and J^T delta on the shared controls (pcl_merit_grad_dev), then ONE sum
               all-reduce of that 5.6 KB payload over the ranks (RCCL) -- all inside the timed region.  One eval = one member.
-  auto        1 GPU: `single` is timed as `value`; the multistart and ensemble shares are measured as well and reported
+  auto        1 GPU: `single` is timed as `value`; with --full the multistart and ensemble shares are measured as well and reported
               in `multistart_share` / `ensemble_share` of the same line (+ `multistart_64`: config 5's 64 seeds on this one GPU,
-              the reference point of the scaling curve).  N > 1 GPUs: BOTH sharded workloads are timed, each in its own
-              barrier-bracketed region: `value` = config 5, the 64-seed multistart with 64 / N seeds per GPU in one launch
-              (STRONG scaling: the total is fixed at 64; no data-path collective), and `ensemble_share` = config 4's 64 members
-              with 64 / N per GPU, whose step contains the ONE RCCL all-reduce (`rccl_ranks`, `all_reduce_us` alone beside it).
+              the reference point of the scaling curve).  N > 1 GPUs: `value` = config 5, the 64-seed multistart with 64 / N seeds
+              per GPU in one launch (STRONG scaling: the total is fixed at 64; no data-path collective); with --full BOTH sharded
+              workloads are timed, each in its own barrier-bracketed region: `ensemble_share` = config 4's 64 members with 64 / N
+              per GPU, whose step contains the ONE RCCL all-reduce (`rccl_ranks`, `all_reduce_us` alone beside it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W]      (N > 1 without a launcher: bench.py starts its own N ranks)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--full] [--dump-outputs DIR]
+                    (N > 1 without a launcher: bench.py starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (contract in the task statement) with the extra objects
+A plain run sets up, warms up, times the K steps of the workload, writes their outputs (--dump-outputs) and prints the line; everything
+else it can measure runs only with --full.  Rank 0 prints ONE JSON line (contract in the task statement) with the extra objects
   roofline      algorithmic HBM bytes per launch / measured kernel time (HIP events on the launch stream) vs 8 TB/s
-  cpu_baseline  the oracle's C restatement (oracle/pade_ref.c, OpenMP) timed on this host (rank 0, N=1)
-  other_rates   Hessian of the Lagrangian, compact Jacobian, residual only, host-delivered (both delivery paths), config 2.
+  cpu_baseline  (--full) the oracle's C restatement (oracle/pade_ref.c, OpenMP) timed on this host (rank 0, N=1)
+  other_rates   (--full) Hessian of the Lagrangian, compact Jacobian, residual only, host-delivered (both delivery paths), config 2.
 `vs_baseline` is null (BASELINE.md holds no published number for this metric); `vs_cpu_baseline` = value / cpu_baseline.value measured in
 the same run (the north star's target is >= 50x the single-socket CPU path), absent when the CPU baseline is skipped.
+--dump-outputs DIR: what the timed path computed in its last step (rank 0), as DIR/<name>.npy (float64): single / multistart
+`residual`, `jacobian_values`; ensemble `objective`, `gradient`, `residual`, `jacobian_values`, `merit_payload`.  An array above
+DUMP_WHOLE values is written as `<name>_sample.npy`, a fixed, seeded sample of it (dump_outputs); the inputs are fixed by the seeds.
 """
 import argparse
 import json
@@ -96,6 +101,31 @@ def time_steps(launch, steps, warmup, torch, dist):
     return wall, ev0.elapsed_time(ev1) * 1e-3
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all arrays together (the .npy headers aside)
+DUMP_WHOLE = 1 << 20  # values: an array up to this size is written whole, a larger one as a sample sharing what is left of DUMP_BYTES
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor, in the order the caller receives them) as float64 .npy files in outdir.  The sample of
+    a large array is a sorted set of indices drawn by a generator seeded with the array's length alone, so two runs with the same arguments
+    (the same inputs, bench.py's seeds are fixed) write the same positions and two builds can be compared value for value."""
+    import torch
+
+    os.makedirs(outdir, exist_ok=True)
+    small = {k: t for k, t in arrays.items() if t.numel() <= DUMP_WHOLE}
+    large = [k for k in arrays if k not in small]
+    left = DUMP_BYTES - 8 * sum(t.numel() for t in small.values())
+    per = left // 8 // max(1, len(large))
+    for name, t in arrays.items():
+        if name in small:
+            a = t.detach().double().cpu().numpy()
+        else:
+            idx = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), size=min(per, t.numel()), replace=False))
+            a = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].double().cpu().numpy()
+            name += "_sample"
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` without a launcher: re-run this very command line under `python -m torch.distributed.run
     --nnodes=1 --nproc-per-node N` (one rank per GPU, rendezvous on 127.0.0.1 at a free port, dmabuf IPC), hand the ranks'
@@ -143,6 +173,10 @@ def main():
     ap.add_argument("--separate-payload", action="store_true", help="ensemble step: pcl_eval_jac_dev + pcl_merit_grad_dev instead of the fused pcl_eval_jac_merit_dev")
     ap.add_argument("--no-extras", action="store_true", help="skip the Hessian / compact / residual-only / host-delivered / config-2 rates")
     ap.add_argument("--no-resident", action="store_true", help="accepted and ignored (round 5's resident evaluator is a lab build now)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the shares, the other orders and rates, the matrix-core pass, the default "
+                    "order's rate, the CPU baseline (1 GPU) and the config-4 step beside the multistart line (N > 1 GPUs); the --no-* switches thin it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the timed path computed in its last step "
+                    "(rank 0) as DIR/<name>.npy, float64; arrays above 1 Mi values are a fixed, seeded sample (<name>_sample.npy), %d MiB in all" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     import torch
@@ -228,10 +262,11 @@ def main():
         t = sorted(ts)
         return {"buffers": len(t), "us_min": t[0], "us_median": t[len(t) // 2], "us_max": t[-1]} if t else {}
 
-    def run_multistart(batch, steps, warmup, use_dist, order=4, nbuf=1, kernel_version=0, ab=()):
+    def run_multistart(batch, steps, warmup, use_dist, order=4, nbuf=1, kernel_version=0, ab=(), keep=None):
         """`batch` independent trajectories in one launch per step (batch 1 = BASELINE config 3 strictly).  nbuf > 1: the same launch on
         nbuf separately allocated values arrays, one after the other; returns the per-array times as info["per_buffer_us"] and the
-        MEDIAN array's (wall, device) times.  ab: names of AB_VARIANTS timed beside the default on every array (info["ab"])."""
+        MEDIAN array's (wall, device) times.  ab: names of AB_VARIANTS timed beside the default on every array (info["ab"]).
+        keep (a dict): receives the outputs of the last step (--dump-outputs)."""
         while len(seeds) < batch:
             seeds.append(synthetic.synthetic_trajectory(system, N, seed=1000 + units_of_rank(batch * world, rank, world)[len(seeds)]))
         ms = pa.HipPadeMultistart(G0, Gj, t0, batch, device=local, pade_order=order)
@@ -270,13 +305,15 @@ def main():
             info["auto_choice_per_buffer"] = tuned
         if ab:
             info["ab"] = {nm: spread_us(v) for nm, v in abres.items()}
+        if keep is not None:  # residual delta and Jacobian values (trajectory after trajectory), as eval_jac_dev leaves them
+            keep.update(residual=dd, jacobian_values=vds[-1])
         ms.close()
         del Zd, dd, vds
         return wall, dev, info
 
-    def run_ensemble(M, steps, warmup, use_dist, nbuf=1, ab=()):
+    def run_ensemble(M, steps, warmup, use_dist, nbuf=1, ab=(), keep=None):
         """Config 4 share: the members i with i mod world == rank of the M * world, shared controls, objective + reduce payload + all-reduce.
-        nbuf > 1, ab: as run_multistart."""
+        nbuf > 1, ab, keep: as run_multistart."""
         members = synthetic.config4_members(0, 0, indices=units_of_rank(M * world, rank, world))
         traj = synthetic.synthetic_ensemble(members, N, seed=20260929 + 4)  # the same shared controls on every rank
         Bs = pa.BilinearIntegrator(members, traj, device=local, pade_order=args.order)
@@ -339,21 +376,29 @@ def main():
             info["per_buffer_us"] = [r[1] / steps * 1e6 for r in res]
         if ab:
             info["ab"] = {nm: spread_us(v) for nm, v in abres.items()}
-        if reduce_:  # the collective alone (same payload, same stream), barrier-bracketed like the step
+        if keep is not None:  # objective, its gradient, residual, Jacobian values, [merit | J^T delta] (all-reduced when the step reduces)
+            # (the payload copied: the collective timed alone below sums into it again)
+            keep.update(objective=payload[:1].clone(), gradient=grad, residual=dd, jacobian_values=vds[-1], merit_payload=payload[1:].clone())
+        if reduce_:
+            info["rccl_ranks"] = int(dist.get_world_size())
+        if reduce_ and args.full:  # the collective alone (same payload, same stream), barrier-bracketed like the step
             wr, dr = time_steps(lambda: pd.reduce_payload(payload, dist), steps, min(warmup, 5), torch, dist)
             info["all_reduce_us"] = dr / steps * 1e6
-            info["rccl_ranks"] = int(dist.get_world_size())
         for b in Bs:
             b.close()
         del Zd, dd, vd, vds, grad
         return wall, dev, info, abytes - t0.dim * 8 * (N - 1) + traj.dim * 8 * (N - 1) // M  # bytes per member eval (Z shared by M members)
 
     units = 1 if workload == "single" else B
+    outputs = {} if args.dump_outputs and rank == 0 else None
     if workload == "ensemble":
-        wall, dev, info, ubytes = run_ensemble(B, args.steps, args.warmup, True)
+        wall, dev, info, ubytes = run_ensemble(B, args.steps, args.warmup, True, keep=outputs)
     else:
-        wall, dev, info = run_multistart(units, args.steps, args.warmup, True, args.order, kernel_version=args.kernel_version)
+        wall, dev, info = run_multistart(units, args.steps, args.warmup, True, args.order, kernel_version=args.kernel_version, keep=outputs)
         ubytes = abytes
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     t = torch.tensor([wall, dev], dtype=torch.float64, device="cuda")
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -398,7 +443,7 @@ def main():
                                             for k, v in json.load(open(pve))["configs"].items()}
         except Exception:
             pass
-    if world > 1 and workload == "multistart" and args.workload == "auto":
+    if args.full and world > 1 and workload == "multistart" and args.workload == "auto":
         # config 4 beside it: 64 / N members per rank, the step that holds the one collective
         we, de, ie, ub = run_ensemble(B, args.steps, args.warmup, True)
         te = torch.tensor([we, de], dtype=torch.float64, device="cuda")
@@ -439,7 +484,7 @@ def main():
             out["roofline"]["mfma_path"] = json.load(open(mf))
         except Exception:
             pass
-    if rank == 0 and world == 1 and workload == "single" and not args.no_extras and not args.kernel_version:
+    if args.full and rank == 0 and world == 1 and workload == "single" and not args.no_extras and not args.kernel_version:
         w3, d3, i3 = run_multistart(1, max(20, min(args.steps, 100)), 40, False, 4, kernel_version=3)
         out["roofline"].setdefault("mfma_path", {})["kernel3_us_per_launch_this_run"] = d3 / max(20, min(args.steps, 100)) * 1e6
         out["roofline"]["mfma_path"]["kernel3_id"] = i3["kernel_id"]
@@ -453,7 +498,7 @@ def main():
         except Exception:
             pass
 
-    if rank == 0 and world == 1 and workload == "single" and not args.no_extras:  # (--no-extras: the profiling passes trace the timed launch alone)
+    if args.full and rank == 0 and world == 1 and workload == "single" and not args.no_extras:  # (--no-extras: the profiling passes trace the timed launch alone)
         # PARITY BY DEFAULT: what the drop-in's default constructor (pade_order = 0: the order policy at 1e-10) evaluates on this problem's
         # bounds (|u| <= 0.1 = the system's drive bounds, dt <= 0.1 = the step of the synthetic trajectories), and its rate -- the rate at
         # the order that matches the reference's exp constraint, beside the order-4 `value` BASELINE.json's metric is quoted on
@@ -484,7 +529,7 @@ def main():
                                         #  shows as wall time far above the HIP-event time of the same region, and is flagged instead of hidden)
                                         "host_stall_in_region": bool(rs["evals_per_s"] * rs["us_per_launch_kernel"] * 1e-6 < 0.67),
                                         "note": "the order HipPadeIntegrator / BilinearIntegrator choose by default (pade_order = 0) on config 3's bounds, one trajectory per launch"}
-    if rank == 0 and world == 1 and args.workload == "auto" and not args.no_shares:
+    if args.full and rank == 0 and world == 1 and args.workload == "auto" and not args.no_shares:
         st = max(20, min(args.steps, 100))
 
         def spread(info):
@@ -532,7 +577,7 @@ def main():
                             "note": "compact producer + replicating expander on one stream against the fused launch of the same 8 seeds (lab/probes/decoupled_probe.py: two streams, seed by seed, is slower still)"}
         msx.close()
         del Zx, dx, cvx, vx
-    if rank == 0 and world == 1 and args.workload == "auto" and not args.no_shares:
+    if args.full and rank == 0 and world == 1 and args.workload == "auto" and not args.no_shares:
         # config 5 whole (64 seeds) on this one GPU in one launch: the N = 1 point of the multistart scaling curve
         T = args.total_units
         w64, d64, i64 = run_multistart(T, 10, 10, False, nbuf=NBUF, ab=("static",))  # (10 untimed launches: the per-array choice of v4_tune is made in them)
@@ -544,7 +589,7 @@ def main():
         out["ensemble_64"] = {"evals_per_s": T * 5 / we64, "us_per_step_kernel": de64 / 5 * 1e6, "members_per_step": T, "z_dim": ie64["z_dim"], **spread_us(ie64.get("per_buffer_us", [])),
                               "frac_of_hbm_peak": ub64 * T / (de64 / 5) / 1e9 / HBM_PEAK_GBS, "launches_per_step": ie64["launches_per_step"], "payload_fused": ie64["payload_fused"],
                               "note": "BASELINE config 4 at its real size (sampling_trajectory.jl:207-237 layout): fused residual+Jacobian of 64 members + objective + payload, no all-reduce (one rank)"}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         try:  # (the headline must be printed whatever happens in here: a failure is reported in the line, not raised)
             # the other rates of the same path, reported beside the headline (never as `value`)
             ex = {}
@@ -684,7 +729,7 @@ def main():
             out["other_rates"] = ex
         except Exception as exc:
             out["other_rates"] = {"error": repr(exc), "partial": {k: v for k, v in locals().get("ex", {}).items()}}
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_cpu_baseline:
             # the C restatement of the oracle on ONE socket of this host, in a process of its own (pinned before its OpenMP runtime starts):
             # bench/cpu_baseline.py -- the checker timed as a comparator, never part of the product path

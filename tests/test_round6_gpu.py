@@ -443,7 +443,7 @@ def test_bench_with_two_ranks_on_one_device():
     env = dict(os.environ)
     env.update(PCL_BENCH_TEST_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]  # fmt: skip
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"]  # fmt: skip
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=1500)
     assert pr.returncode == 0, pr.stderr.decode()[-3000:]
     lines = [ln for ln in pr.stdout.decode().splitlines() if ln.strip()]
