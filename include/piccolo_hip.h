@@ -14,6 +14,10 @@
  *                         (copies G_drift / G_drives of sys.G, quantum_systems.jl:225-226,
  *                          composite_quantum_systems.jl:124-132, and the component ranges of the
  *                          NamedTrajectory, named_trajectory_conversion.jl:339-351)
+ *   pcl_create            VariationalUnitaryIntegrator(sys, traj, :U, [:U_var, ...], :u; scales)   src/control/integrators.jl:247-264
+ *                         VariationalKetIntegrator(sys, traj, :psi, [:psi_var, ...], :u; scale)    src/control/integrators.jl:234-245
+ *                         (batch_mode PCL_BATCH_VARIATIONAL; VariationalQuantumSystem, variational_quantum_systems.jl:66-124;
+ *                          generator var_G(G(u), [G_var_i / scale_i]), isomorphisms.jl:398-422)
  *   pcl_constraint_dim    B.dim == x_dim*(N-1), B.x_dim                        src/control/integrators.jl:307-309
  *   pcl_eval[_dev]        evaluate!(delta, B, traj) [EXT]                      src/control/integrators.jl:311,777
  *   pcl_jac_nnz/structure jacobian structure handed to MOI [EXT]; shape pin    src/control/integrators.jl:780-783
@@ -87,6 +91,22 @@ typedef enum pcl_status {
 #define PCL_STATE_VECTOR (-1) /* pcl_desc.state_cols: see there */
 #define PCL_BATCH_TRAJ 1    /* batch independent trajectory buffers (multistart seeds), Z_b = Z + b*z_dim*N;
                                x_offs[0] is the state offset in each */
+#define PCL_BATCH_VARIATIONAL 2 /* the variational (sensitivity) integrators: ONE trajectory whose state is the stack [X; Xv_1; ...; Xv_v]
+                               of the state and its first-order sensitivities to v perturbation directions (v = 1, 2 for d <= 32; more:
+                               PCL_ESHAPE), evolved by the lifted generator var_G(G(u), [Gv_i]) = [[G, 0..], [Gv_1, G, 0..], .., [Gv_v, 0.., G]]
+                               per state column.  batch = 1 + v; x_offs[0] the state, x_offs[i] variation i; per_member_G0 = 1 with
+                               G0[0] = G_drift and G0[i] = Gv_i = G(H_var_i) / scale_i (the caller applies the scales); state_cols d
+                               (unitary) or 1 (ket), not PCL_STATE_VECTOR.
+                               x_dim (pcl_constraint_dim) is the stacked (1 + v) n C.  Rows are KNOT-major over the stacked state,
+                               row k*x_dim + b*(n C) + c*n + i (component b, state column c) -- the reference's B.dim = x_dim (N-1) -- and
+                               NOT the member-major order of PCL_BATCH_MEMBERS.  Jacobian values per interval (pcl_jac_structure):
+                                 -B^+ and B^- of delta_0 (C n^2 each, I_C (x) .), then per variation i: -B^+ (Xv_i,k), B^- (Xv_i,k+1),
+                                 -L^+_i (X_k), L^-_i (X_{k+1}) with L^{+-}_i = sum_{j>=1} c_j (+-h)^j Q_j^i the (i,0) blocks of the
+                                 lifted powers; then the tails, (m+1) n per state column for each of the 1 + v components (component-major)
+                               -- (2 + 4v) C n^2 + x_dim (m+1) values, no structural zeros.  Hessian: the segments below over the stacked
+                               state.  Entry points: create, dimensions, structures, pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev],
+                               pcl_hess[_dev] (host-pointer calls deliver full values), the order policy (theta of the lifted generator),
+                               streams, options, pcl_deriv_*; every other entry point returns PCL_ENOTIMPL. */
 
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
@@ -97,7 +117,7 @@ typedef struct pcl_desc {
     int32_t u_off;       /* 0-based offset of the drive component inside a knot (traj.components[:u][1]-1) */
     int32_t dt_off;      /* 0-based offset of the timestep component */
     int32_t batch;       /* number of members / seeds (>= 1) */
-    int32_t batch_mode;  /* PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ */
+    int32_t batch_mode;  /* PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ or PCL_BATCH_VARIATIONAL */
     int32_t pade_order;  /* diagonal Pade order p of B^{+-}_p: 2, 4, 6, 8 or 10; 0: the smallest order whose deviation from the reference's
                             exp constraint is below a tolerance -- pcl_set_order_policy, or the first host-pointer call decides */
     int32_t device_id;   /* HIP device ordinal */

@@ -12,6 +12,9 @@ from .integrators import (
     HipPadeIntegrator,
     HipPadeMemberIntegrator,
     HipPadeMultistart,
+    HipVariationalIntegrator,
+    VariationalKetIntegrator,
+    VariationalUnitaryIntegrator,
     eval_hessian_of_lagrangian,
     eval_jacobian,
     evaluate_,
@@ -31,6 +34,7 @@ from .quantum import (
     QuantumSystem,
     TransmonDipoleCoupling,
     TransmonSystem,
+    VariationalQuantumSystem,
     annihilate,
     compact_iso_to_density,
     density_to_compact_iso,

@@ -140,6 +140,7 @@ static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int
     return set_form(ctx, 0, R, A.data(), nullptr, false);
 }
 extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c) {
+    VAR_NOTIMPL(ctx, "pcl_set_goal_form");
     if (!ctx) return PCL_EINVAL;
     if (scope != 0 && scope != 1) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: scope must be 0 (per member) or 1 (joint)");
     if (scope == 1 && ctx->desc.batch_mode != PCL_BATCH_MEMBERS) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: a joint term needs the members of ONE trajectory buffer");
@@ -152,6 +153,7 @@ extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const d
     return set_form(ctx, scope, R, A, c, true);
 }
 extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
+    VAR_NOTIMPL(ctx, "pcl_set_goal");
     if (!ctx) return PCL_EINVAL;
     if (!goal_iso_vec) return fail(ctx, PCL_EINVAL, "pcl_set_goal: NULL");
     TRY(objective_unitary_only(ctx, "pcl_set_goal"));
@@ -166,6 +168,7 @@ extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
     return unitary_form(ctx, goal_iso_vec);
 }
 extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns) {
+    VAR_NOTIMPL(ctx, "pcl_set_goal_subspace");
     if (!ctx) return PCL_EINVAL;
     if (!goal_sub_iso_vec || !subspace) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: NULL");
     TRY(objective_unitary_only(ctx, "pcl_set_goal_subspace"));
@@ -191,6 +194,7 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
 }
 extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
+    VAR_NOTIMPL(ctx, "pcl_set_weights");
     if (!ctx) return PCL_EINVAL;
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -205,6 +209,7 @@ extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
     return PCL_OK;
 }
 extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const double *R, int32_t dt_power) {
+    VAR_NOTIMPL(ctx, "pcl_add_regularizer");
     if (!ctx) return PCL_EINVAL;
     if (!R || dim < 1 || off < 0 || off + dim > ctx->desc.z_dim) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: component [%d, %d) outside the knot (z_dim=%d)", off, off + dim, ctx->desc.z_dim);
     if (dt_power < 0 || dt_power > 2) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: dt_power must be 0, 1 or 2");
@@ -216,6 +221,7 @@ extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const
     return PCL_OK;
 }
 extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
+    VAR_NOTIMPL(ctx, "pcl_clear_regularizers");
     if (!ctx) return PCL_EINVAL;
     ctx->regs.clear();
     ctx->reg_R.clear();
@@ -224,6 +230,7 @@ extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
 }
 static unsigned infidelity_lds(const pcl_ctx *ctx) { return (unsigned)(6 * (size_t)ctx->n_sub * ctx->n_sub * sizeof(double)); }
 extern "C" int pcl_infidelity_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    VAR_NOTIMPL(ctx, "pcl_infidelity_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || (!value && !grad)) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: call pcl_set_goal first");
@@ -270,6 +277,7 @@ static int objective_prepare(pcl_ctx *ctx) {
 static bool tail_applies(const pcl_ctx *ctx, const double *grad, int &lo_, int &hi_);
 static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad, int skip_lo, int skip_hi, double *merit_out);
 extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    VAR_NOTIMPL(ctx, "pcl_objective_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective_dev: NULL pointer");
     if (!ctx->dgoal && !ctx->form_user && ctx->regs.empty()) return fail(ctx, PCL_EINVAL, "pcl_objective_dev: no goal and no regulariser set");
@@ -326,6 +334,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
     return PCL_OK;
 }
 extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    VAR_NOTIMPL(ctx, "pcl_objective");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective: NULL pointer");
     ON_DEVICE(ctx);
@@ -342,6 +351,7 @@ extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *va
 }
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
+    VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
     if (!ctx) return PCL_EINVAL;
     if (!delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_merit_grad_dev: NULL pointer");
     ON_DEVICE(ctx);
@@ -361,6 +371,7 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 }
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
+    VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");
     ctx->merit_want = 1;
@@ -411,12 +422,14 @@ static long long obj_hess_per_knot(const pcl_ctx *ctx) {
     return n;
 }
 extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
+    VAR_NOTIMPL(ctx, "pcl_objective_hess_nnz");
     if (!ctx || !nnz) return PCL_EINVAL;
     const int nbuf = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;
     *nnz = obj_hess_terms(ctx) * obj_hess_tri(ctx) + (long long)nbuf * ctx->desc.N * obj_hess_per_knot(ctx);
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols) {
+    VAR_NOTIMPL(ctx, "pcl_objective_hess_structure");
     if (!ctx || !rows || !cols) return PCL_EINVAL;
     const pcl_desc &D = ctx->desc;
     const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
@@ -449,6 +462,7 @@ extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, i
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
+    VAR_NOTIMPL(ctx, "pcl_objective_hess_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess_dev: NULL pointer");
     ON_DEVICE(ctx);
@@ -482,6 +496,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
+    VAR_NOTIMPL(ctx, "pcl_objective_hess");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess: NULL pointer");
     ON_DEVICE(ctx);
@@ -574,6 +589,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 // regulariser rows, the terminal infidelities and the payload's finish (pcl_ens_tail_kernel); the same bits as the separate calls.
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
+    VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out || !value) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: no goal set");
@@ -602,6 +618,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
     return PCL_OK;
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
+    VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
     if (!ctx) return PCL_EINVAL;
     if (len) *len = 1 + (int64_t)ctx->K * ctx->desc.n_drives + ctx->K;
     if (sets) *sets = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;

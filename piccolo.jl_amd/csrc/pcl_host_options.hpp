@@ -15,6 +15,10 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     }
     else if (!strcmp(key, "grid"))
         ctx->opt_grid = v;
+    else if (!strcmp(key, "var_block_wgs") || !strcmp(key, "var_col_wgs")) {  // variational contexts: workgroups per interval of the fused launch (0 auto)
+        if (v < 0) return fail(ctx, PCL_EINVAL, "%s must be >= 0", key);
+        (key[4] == 'b' ? ctx->opt_var_blocks : ctx->opt_var_cols) = v;
+    }
 #ifdef PCL_PROFILE
     else if (!strcmp(key, "profile_flags"))  // profiling experiments (results may be WRONG); not present in the shipped library
         ctx->opt_prof = v;
@@ -142,6 +146,12 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
                  : choose_cols_per_slice(ctx, true);
     else if (!strcmp(key, "n_cu"))
         *v = ctx->n_cu;
+    else if (!strcmp(key, "var_block_wgs"))
+        *v = ctx->var ? var_split_blocks(ctx) : ctx->opt_var_blocks;
+    else if (!strcmp(key, "var_col_wgs"))
+        *v = ctx->var ? var_split_cols(ctx) : ctx->opt_var_cols;
+    else if (!strcmp(key, "variations"))
+        *v = ctx->var;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

@@ -1,0 +1,406 @@
+// pcl_host_variational.hpp -- part of piccolo_hip.hip (included there, in place, before pcl_create): batch_mode PCL_BATCH_VARIATIONAL, the
+// variational (sensitivity) integrators VariationalUnitaryIntegrator / VariationalKetIntegrator (src/control/integrators.jl:234-264): creation and
+// validation, structures, and the launches of pcl_kernel_variational.hpp.
+#pragma once
+#include "pcl_kernel_variational.hpp"
+
+// Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
+static long long var_jac_per(const pcl_ctx *c) {
+    return (2LL + 4LL * c->var) * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
+}
+
+// Validation of a variational descriptor: every check runs before any device call; the message names the field.
+static int var_validate(const pcl_desc *D) {
+    const int d = D->d, m = D->n_drives;
+    if (D->batch < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: batch=%d; PCL_BATCH_VARIATIONAL takes batch = 1 + v with v >= 1 variations", D->batch);
+    if (D->per_member_G0 != 1)
+        return fail(nullptr, PCL_EINVAL, "pcl_create: per_member_G0=%d; PCL_BATCH_VARIATIONAL takes per_member_G0 = 1 (G0[0] = G_drift, G0[i] = Gv_i)", D->per_member_G0);
+    if (D->state_cols == PCL_STATE_VECTOR) return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=PCL_STATE_VECTOR is not supported by PCL_BATCH_VARIATIONAL");
+    if (d < 1) return fail(nullptr, PCL_EINVAL, "pcl_create: d=%d", d);
+    if (D->state_cols != 0 && D->state_cols != 1 && D->state_cols != d)
+        return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=%d; PCL_BATCH_VARIATIONAL takes d (unitary, or 0) or 1 (ket)", D->state_cols);
+    if (m < 0) return fail(nullptr, PCL_EINVAL, "pcl_create: n_drives=%d", m);
+    if (D->N < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: N=%d; need N >= 2", D->N);
+    if (D->pade_order != 0 && D->pade_order != 2 && D->pade_order != 4 && D->pade_order != 6 && D->pade_order != 8 && D->pade_order != 10)
+        return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order=%d; diagonal Pade orders 2, 4, 6, 8, 10 are implemented (0: chosen by pcl_set_order_policy)", D->pade_order);
+    if (D->index_base != 0 && D->index_base != 1) return fail(nullptr, PCL_EINVAL, "pcl_create: index_base=%d; must be 0 or 1", D->index_base);
+    if (D->global_dim < 0) return fail(nullptr, PCL_EINVAL, "pcl_create: global_dim=%lld", (long long)D->global_dim);
+    if (!D->G0) return fail(nullptr, PCL_EINVAL, "pcl_create: G0 is NULL");
+    if (m > 0 && !D->Gj) return fail(nullptr, PCL_EINVAL, "pcl_create: Gj is NULL");
+    if (!D->x_offs) return fail(nullptr, PCL_EINVAL, "pcl_create: x_offs is NULL");
+    const int cols = D->state_cols > 0 ? D->state_cols : d;
+    const long long x_dim = 2LL * d * cols;
+    for (int b = 0; b < D->batch; ++b) {
+        if (D->x_offs[b] < 0 || D->x_offs[b] + x_dim > D->z_dim)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: x_offs[%d]=%d with x_dim=%lld does not fit z_dim=%d", b, D->x_offs[b], x_dim, D->z_dim);
+        for (int a = 0; a < b; ++a)
+            if (std::llabs((long long)D->x_offs[a] - D->x_offs[b]) < x_dim)
+                return fail(nullptr, PCL_EINVAL, "pcl_create: x_offs[%d]=%d and x_offs[%d]=%d overlap (x_dim=%lld)", a, D->x_offs[a], b, D->x_offs[b], x_dim);
+    }
+    if (D->u_off < 0 || D->u_off + m > D->z_dim) return fail(nullptr, PCL_EINVAL, "pcl_create: u_off=%d with n_drives=%d outside the knot (z_dim=%d)", D->u_off, m, D->z_dim);
+    if (D->dt_off < 0 || D->dt_off >= D->z_dim) return fail(nullptr, PCL_EINVAL, "pcl_create: dt_off=%d outside the knot (z_dim=%d)", D->dt_off, D->z_dim);
+    for (int b = 0; b < D->batch; ++b) {
+        const long long xo = D->x_offs[b];
+        if ((D->u_off < xo + x_dim && xo < D->u_off + m) || (D->dt_off >= xo && D->dt_off < xo + x_dim))
+            return fail(nullptr, PCL_EINVAL, "pcl_create: x_offs[%d]=%d overlaps u_off / dt_off", b, D->x_offs[b]);
+    }
+    // shapes the kernels take
+    if (d > PCL_MAX_D) return fail(nullptr, PCL_ESHAPE, "pcl_create: d=%d exceeds %d (LDS-resident generator tiles)", d, PCL_MAX_D);
+    if (D->batch - 1 > PCL_VAR_MAXV) return fail(nullptr, PCL_ESHAPE, "pcl_create: %d variations; PCL_BATCH_VARIATIONAL takes at most %d", D->batch - 1, PCL_VAR_MAXV);
+    if (m > 24) return fail(nullptr, PCL_ESHAPE, "pcl_create: n_drives=%d exceeds 24", m);
+    return PCL_OK;
+}
+
+static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
+    if (int rc = var_validate(dsc)) return rc;
+    const int d = dsc->d, m = dsc->n_drives, n = 2 * d, v = dsc->batch - 1;
+    const int cols = dsc->state_cols > 0 ? dsc->state_cols : d;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return fail(nullptr, PCL_EHIP, "pcl_create: no HIP device available (%s); this library has no CPU path", e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    if (dsc->device_id < 0 || dsc->device_id >= ndev) return fail(nullptr, PCL_EINVAL, "pcl_create: device_id %d of %d", dsc->device_id, ndev);
+    pcl_ctx *ctx = new (std::nothrow) pcl_ctx();
+    if (!ctx) return fail(nullptr, PCL_ENOMEM, "pcl_create: out of host memory");
+    const size_t nn = (size_t)n * n;
+    ctx->desc = *dsc;
+    ctx->var = v;
+    ctx->n = n;
+    ctx->K = dsc->N - 1;
+    ctx->cols = cols;
+    ctx->var_xdc = (long long)n * cols;
+    ctx->x_dim = ctx->var_xdc * (v + 1);  // the stacked state: B.x_dim of the reference
+    ctx->x_offs.assign(dsc->x_offs, dsc->x_offs + v + 1);
+    ctx->win_first = 0;
+    ctx->win_count = 1;
+    ctx->device = dsc->device_id;
+    // the order policy looks at the lifted generator: G0' = var_G(G_drift, [Gv_i]), G_l' = I_{1+v} (x) G_l
+    const int nl = (v + 1) * n;
+    ctx->var_nl = nl;
+    ctx->hG0.assign((size_t)nl * nl, 0.0);
+    for (int b = 0; b <= v; ++b)
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) {
+                ctx->hG0[(size_t)(b * n + i) + (size_t)nl * (b * n + j)] = dsc->G0[i + (size_t)n * j];
+                if (b > 0) ctx->hG0[(size_t)(b * n + i) + (size_t)nl * j] = dsc->G0[(size_t)b * nn + i + (size_t)n * j];
+            }
+    ctx->hGj.assign((size_t)m * nl * nl, 0.0);
+    for (int l = 0; l < m; ++l)
+        for (int b = 0; b <= v; ++b)
+            for (int j = 0; j < n; ++j)
+                for (int i = 0; i < n; ++i) ctx->hGj[(size_t)l * nl * nl + (b * n + i) + (size_t)nl * (b * n + j)] = dsc->Gj[(size_t)l * nn + i + (size_t)n * j];
+    ctx->desc.x_offs = nullptr;
+    ctx->desc.G0 = ctx->desc.Gj = nullptr;
+    // device tables: [G_drift | G_l (m) | Gv_i (v) | the same transposed], n x n column-major each
+    const size_t nmat = 1 + (size_t)m + v;
+    std::vector<double> tab(2 * nmat * nn);
+    auto mat = [&](size_t i) -> const double * { return i == 0 ? dsc->G0 : i <= (size_t)m ? dsc->Gj + (i - 1) * nn : dsc->G0 + (i - m) * nn; };
+    for (size_t t = 0; t < nmat; ++t)
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) {
+                tab[t * nn + i + (size_t)n * j] = mat(t)[i + (size_t)n * j];
+                tab[(nmat + t) * nn + i + (size_t)n * j] = mat(t)[j + (size_t)n * i];
+            }
+#define VAR_HIP(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e2_ = (expr);                                                                   \
+        if (e2_ != hipSuccess) {                                                                   \
+            fail(nullptr, PCL_EHIP, "pcl_create: %s: %s", #expr, hipGetErrorString(e2_));          \
+            pcl_destroy(ctx);                                                                      \
+            return PCL_EHIP;                                                                       \
+        }                                                                                          \
+    } while (0)
+    DeviceGuard dev_guard_(ctx->device);
+    VAR_HIP(dev_guard_.err);
+    hipDeviceProp_t prop;
+    VAR_HIP(hipGetDeviceProperties(&prop, ctx->device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        fail(nullptr, PCL_EHIP, "pcl_create: device %d is %s; this library is built for gfx950 only", ctx->device, prop.gcnArchName);
+        pcl_destroy(ctx);
+        return PCL_EHIP;
+    }
+    ctx->max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
+    ctx->n_cu = prop.multiProcessorCount;
+    VAR_HIP(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    ctx->stream = ctx->own_stream;
+    // row-compressed (ELL) tables of the column role, [slot t][row i], padded with column 0 / value 0: G(u) on the union pattern of the drift
+    // and the drives (a value table per matrix), then every drive, then every variation generator (each group padded to its widest row)
+    std::vector<int> icol;
+    std::vector<double> ival;
+    auto pattern = [&](const std::vector<const double *> &mats) {
+        std::vector<std::vector<int>> rows(n);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) {
+                bool nz = false;
+                for (const double *A : mats) nz |= A[i + (size_t)n * j] != 0.0;
+                if (nz) rows[i].push_back(j);
+            }
+        return rows;
+    };
+    auto width = [&](const std::vector<const double *> &mats) {
+        int w = 1;
+        for (const auto &r : pattern(mats)) w = std::max<int>(w, (int)r.size());
+        return w;
+    };
+    auto append = [&](const std::vector<const double *> &mats, int w) {
+        const auto rows = pattern(mats);
+        const size_t c0 = icol.size(), v0 = ival.size();
+        icol.resize(c0 + (size_t)w * n, 0);
+        ival.resize(v0 + mats.size() * (size_t)w * n, 0.0);
+        for (int i = 0; i < n; ++i)
+            for (size_t t = 0; t < rows[i].size(); ++t) {
+                icol[c0 + t * n + i] = rows[i][t];
+                for (size_t a = 0; a < mats.size(); ++a) ival[v0 + (a * w + t) * n + i] = mats[a][i + (size_t)n * rows[i][t]];
+            }
+    };
+    std::vector<const double *> gm{dsc->G0}, dm, vm;
+    for (int l = 0; l < m; ++l) gm.push_back(dsc->Gj + (size_t)l * nn), dm.push_back(dsc->Gj + (size_t)l * nn);
+    for (int b = 1; b <= v; ++b) vm.push_back(dsc->G0 + (size_t)b * nn);
+    ctx->var_wG = width(gm);
+    append(gm, ctx->var_wG);
+    ctx->var_off_d = (long long)icol.size();
+    ctx->var_voff_d = (long long)ival.size();
+    ctx->var_wD = 1;
+    for (const double *A : dm) ctx->var_wD = std::max(ctx->var_wD, width({A}));
+    for (const double *A : dm) append({A}, ctx->var_wD);
+    ctx->var_off_v = (long long)icol.size();
+    ctx->var_voff_v = (long long)ival.size();
+    ctx->var_wV = 1;
+    for (const double *A : vm) ctx->var_wV = std::max(ctx->var_wV, width({A}));
+    for (const double *A : vm) append({A}, ctx->var_wV);
+    if (upload(ctx, &ctx->dvar_tab, tab) != PCL_OK || upload(ctx, &ctx->dvar_ecol, icol) != PCL_OK || upload(ctx, &ctx->dvar_eval, ival) != PCL_OK) {
+        g_create_error = ctx->err;
+        pcl_destroy(ctx);
+        return PCL_EHIP;
+    }
+    VAR_HIP(hipHostMalloc((void **)&ctx->herr, 64, hipHostMallocMapped));
+    *ctx->herr = 0;
+    VAR_HIP(hipHostGetDevicePointer((void **)&ctx->derr, ctx->herr, 0));
+#undef VAR_HIP
+    *out = ctx;
+    return PCL_OK;
+}
+
+// Rows knot-major over the stacked state: k x_dim' + b x_dim + c n + i (the reference's B.dim = x_dim' (N - 1)).
+template <class I>
+static int var_jac_structure(const pcl_ctx *ctx, I *rows, I *cols) {
+    const pcl_desc &D = ctx->desc;
+    const long long n = ctx->n, C = ctx->cols, m = D.n_drives, xdc = ctx->var_xdc, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
+    const long long per = var_jac_per(ctx);
+    const int v = ctx->var;
+    for (long long k = 0; k < ctx->K; ++k) {
+        I *r = rows + k * per, *c = cols + k * per;
+        long long p = 0;
+        auto block = [&](int brow, int bcol, int knot) {  // I_C (x) (n x n) block: rows of component brow, state columns of component bcol at knot
+            const long long r0 = k * xd + brow * xdc + base, c0 = (k + knot) * zd + ctx->x_offs[bcol] + base;
+            for (long long cc = 0; cc < C; ++cc)
+                for (long long j = 0; j < n; ++j)
+                    for (long long i = 0; i < n; ++i, ++p) {
+                        r[p] = (I)(r0 + cc * n + i);
+                        c[p] = (I)(c0 + cc * n + j);
+                    }
+        };
+        block(0, 0, 0);
+        block(0, 0, 1);
+        for (int b = 1; b <= v; ++b) {
+            block(b, b, 0);
+            block(b, b, 1);
+            block(b, 0, 0);
+            block(b, 0, 1);
+        }
+        for (int b = 0; b <= v; ++b)
+            for (long long cc = 0; cc < C; ++cc)
+                for (long long l = 0; l <= m; ++l) {
+                    const long long col = k * zd + (l < m ? D.u_off + l : D.dt_off) + base;
+                    for (long long i = 0; i < n; ++i, ++p) {
+                        r[p] = (I)(k * xd + b * xdc + cc * n + i + base);
+                        c[p] = (I)col;
+                    }
+                }
+    }
+    return PCL_OK;
+}
+
+// Today's segment order (pcl_hess_structure) over the stacked state: entry q of the state is component q / x_dim, offset q % x_dim.
+template <class I>
+static int var_hess_structure(const pcl_ctx *ctx, I *rows, I *cols) {
+    const pcl_desc &D = ctx->desc;
+    const long long m = D.n_drives, xd = ctx->x_dim, xdc = ctx->var_xdc, zd = D.z_dim, base = D.index_base;
+    const long long per = hess_per(ctx);
+    for (long long k = 0; k < ctx->K; ++k) {
+        I *r = rows + k * per, *c = cols + k * per;
+        const long long uk = k * zd + D.u_off, hk = k * zd + D.dt_off;
+        auto xk = [&](long long q, int knot) { return (k + knot) * zd + ctx->x_offs[q / xdc] + q % xdc; };
+        long long p = 0;
+        auto put = [&](long long a, long long bb) {
+            r[p] = (I)(std::max(a, bb) + base);
+            c[p] = (I)(std::min(a, bb) + base);
+            ++p;
+        };
+        for (long long i = 0; i < m; ++i)
+            for (long long j = 0; j <= i; ++j) put(uk + i, uk + j);
+        for (long long j = 0; j < m; ++j) put(hk, uk + j);
+        put(hk, hk);
+        for (long long l = 0; l < m; ++l)
+            for (long long q = 0; q < xd; ++q) put(uk + l, xk(q, 0));
+        for (long long q = 0; q < xd; ++q) put(hk, xk(q, 0));
+        for (long long l = 0; l < m; ++l)
+            for (long long q = 0; q < xd; ++q) put(xk(q, 1), uk + l);
+        for (long long q = 0; q < xd; ++q) put(xk(q, 1), hk);
+    }
+    return PCL_OK;
+}
+
+static void var_fill(const pcl_ctx *ctx, VarParams &p) {
+    memset(&p, 0, sizeof p);
+    const pcl_desc &D = ctx->desc;
+    const int m = D.n_drives, v = ctx->var;
+    const size_t nn = (size_t)ctx->n * ctx->n, nmat = 1 + (size_t)m + v;
+    p.G0 = ctx->dvar_tab;
+    p.Gj = ctx->dvar_tab + nn;
+    p.Gv = ctx->dvar_tab + (1 + m) * nn;
+    p.G0T = ctx->dvar_tab + nmat * nn;
+    p.GjT = p.G0T + nn;
+    p.GvT = p.G0T + (1 + m) * nn;
+    p.gcol = ctx->dvar_ecol;
+    p.gval = ctx->dvar_eval;
+    p.dcol = ctx->dvar_ecol + ctx->var_off_d;
+    p.dval = ctx->dvar_eval + ctx->var_voff_d;
+    p.vcol = ctx->dvar_ecol + ctx->var_off_v;
+    p.vval = ctx->dvar_eval + ctx->var_voff_v;
+    p.wG = ctx->var_wG;
+    p.wD = ctx->var_wD;
+    p.wV = ctx->var_wV;
+    p.jper = var_jac_per(ctx);
+    p.hper = hess_per(ctx);
+    p.n = ctx->n;
+    p.cols = ctx->cols;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    for (int b = 0; b <= v; ++b) p.xo[b] = ctx->x_offs[b];
+    const int order = D.pade_order, q = order / 2;
+    double f[12];
+    f[0] = 1.0;
+    for (int i = 1; i < 12; ++i) f[i] = f[i - 1] * i;
+    for (int j = 0; j <= q; ++j) p.c[j] = f[2 * q - j] * f[q] / (f[2 * q] * f[j] * f[q - j]);
+}
+
+template <int V, int Q>
+static const void *var_fused_fn(bool jac) {
+    return jac ? (const void *)pcl_var_fused_kernel<V, Q, true> : (const void *)pcl_var_fused_kernel<V, Q, false>;
+}
+static const void *var_pick_fused(int v, int q, bool jac) {
+#define VAR_Q(V)                                            \
+    switch (q) {                                            \
+        case 1: return var_fused_fn<V, 1>(jac);             \
+        case 2: return var_fused_fn<V, 2>(jac);             \
+        case 3: return var_fused_fn<V, 3>(jac);             \
+        case 4: return var_fused_fn<V, 4>(jac);             \
+        case 5: return var_fused_fn<V, 5>(jac);             \
+    }
+    if (v == 1) { VAR_Q(1) }
+    if (v == 2) { VAR_Q(2) }
+#undef VAR_Q
+    return nullptr;
+}
+static const void *var_pick_hess(int v, int q) {
+#define VAR_Q(V)                                                     \
+    switch (q) {                                                     \
+        case 1: return (const void *)pcl_var_hess_kernel<V, 1>;      \
+        case 2: return (const void *)pcl_var_hess_kernel<V, 2>;      \
+        case 3: return (const void *)pcl_var_hess_kernel<V, 3>;      \
+        case 4: return (const void *)pcl_var_hess_kernel<V, 4>;      \
+        case 5: return (const void *)pcl_var_hess_kernel<V, 5>;      \
+    }
+    if (v == 1) { VAR_Q(1) }
+    if (v == 2) { VAR_Q(2) }
+#undef VAR_Q
+    return nullptr;
+}
+
+static int var_set_lds(pcl_ctx *ctx, const void *f, size_t lds) {
+    if (lds > (size_t)ctx->max_lds) return fail(ctx, PCL_ESHAPE, "variational kernel: %zu bytes of LDS exceed the %d of a CU", lds, ctx->max_lds);
+    HIP_TRY(ctx, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return PCL_OK;
+}
+
+// Work split of the fused launch: block workgroups per interval (each folds the powers, then streams a contiguous range of the C copies) and column
+// workgroups (eight waves, one state column each).  Auto: every column its own wave; ONE block workgroup per interval, so the powers are folded
+// once -- measured at config 3 (N = 100): 137 / 134 / 142 / 219 us for 1 / 2 / 7 / 27 block workgroups at order 4 (v = 1), 208 / 281 / 425 / 895
+// at order 10 (profiles/variational_bench_line.json).  Options var_block_wgs / var_col_wgs override; every split gives the same bits.
+static int var_split_blocks(const pcl_ctx *ctx) {
+    const int C = ctx->cols;
+    const int a = ctx->opt_var_blocks > 0 ? (int)ctx->opt_var_blocks : 1;
+    return std::max(1, std::min(a, C));
+}
+static int var_split_cols(const pcl_ctx *ctx) {
+    const int C = ctx->cols, w = PCL_VAR_THREADS / 64;
+    const int a = ctx->opt_var_cols > 0 ? (int)ctx->opt_var_cols : (C + w - 1) / w;
+    return std::max(1, std::min(a, C));
+}
+
+static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+    ON_DEVICE(ctx);
+    if (ctx->desc.pade_order == 0)
+        return fail(ctx, PCL_EINVAL, "pcl_eval / pcl_jac: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
+    VarParams p;
+    var_fill(ctx, p);
+    p.Z = Z;
+    p.delta = delta;
+    p.vals = vals;
+    const bool jac = vals != nullptr;
+    p.nbw = jac ? var_split_blocks(ctx) : 0;
+    p.ncw = var_split_cols(ctx);
+    const void *f = var_pick_fused(ctx->var, ctx->desc.pade_order / 2, jac);
+    if (!f) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: no variational kernel for v=%d, order %d", ctx->var, ctx->desc.pade_order);
+    const size_t nn = (size_t)ctx->n * ctx->n;
+    // block role: G, P, Q_i tiles; column role: the row-compressed values of G(u_k)
+    const size_t lds = std::max(jac ? (2 + ctx->var) * nn : 0, (size_t)ctx->var_wG * ctx->n) * sizeof(double);
+    if (int rc = var_set_lds(ctx, f, lds)) return rc;
+    const long long grid = (long long)ctx->K * (p.nbw + p.ncw);
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
+    void *args[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3(PCL_VAR_THREADS), args, lds, ctx->stream));
+    ctx->last_kernel = jac ? 70 : 71;
+    return PCL_OK;
+}
+
+// LDS of the Hessian kernel with w waves: G, G^T | w slabs of V_{l,j} | w rows of m^2 + m + 1 sums
+static size_t var_hess_lds(const pcl_ctx *ctx, int q, int w) {
+    const size_t m = ctx->desc.n_drives;
+    return (2 * (size_t)ctx->n * ctx->n + (size_t)w * (m * q * (ctx->var + 1) * 64 + m * m + m + 1)) * sizeof(double);
+}
+
+static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    ON_DEVICE(ctx);
+    if (ctx->desc.pade_order == 0)
+        return fail(ctx, PCL_EINVAL, "pcl_hess: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
+    const int q = ctx->desc.pade_order / 2;
+    VarParams p;
+    var_fill(ctx, p);
+    p.Z = Z;
+    p.mu = mu;
+    p.hess = hess;
+    // waves per workgroup: as many as the LDS and the state columns allow, at most 8 (a function of the shape only: the sums' order is fixed)
+    int w = std::min(8, ctx->cols);
+    while (w > 1 && var_hess_lds(ctx, q, w) > (size_t)ctx->max_lds) --w;
+    if (var_hess_lds(ctx, q, w) > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "pcl_hess: the variational Hessian's tiles (%zu bytes at order %d) exceed the LDS", var_hess_lds(ctx, q, w), ctx->desc.pade_order);
+    p.hw = w;
+    const void *f = var_pick_hess(ctx->var, q);
+    if (!f) return fail(ctx, PCL_ESHAPE, "pcl_hess: no variational kernel for v=%d, order %d", ctx->var, ctx->desc.pade_order);
+    const size_t lds = var_hess_lds(ctx, q, w);
+    if (int rc = var_set_lds(ctx, f, lds)) return rc;
+    void *args[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)ctx->K), dim3(64 * w), args, lds, ctx->stream));
+    ctx->last_hess_kernel = 70;
+    return PCL_OK;
+}
+
+#define VAR_NOTIMPL(ctx, what)                                                                                                         \
+    do {                                                                                                                               \
+        if ((ctx) && (ctx)->var) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (PCL_BATCH_VARIATIONAL)", what); \
+    } while (0)

@@ -57,6 +57,15 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
+    int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
+    long long var_xdc = 0;  // ... x_dim of one component
+    int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
+    double *dvar_tab = nullptr;  // ... [G_drift | G_l | Gv_i | the same transposed], n x n column-major each
+    int *dvar_ecol = nullptr;       // ... row-compressed tables of the column role: G(u)'s union pattern, the drives, the variation generators
+    double *dvar_eval = nullptr;
+    int var_wG = 0, var_wD = 0, var_wV = 0;
+    long long var_off_d = 0, var_voff_d = 0, var_off_v = 0, var_voff_v = 0;
+    int64_t opt_var_blocks = 0, opt_var_cols = 0;  // ... block / column workgroups per interval of the fused launch (0 auto)
     long long x_dim;
     std::vector<int32_t> x_offs;
     int device;
@@ -291,7 +300,9 @@ static int v4_power_tiles(int d, int m, int q, size_t max_lds) {
     return v4_lds_bytes(d, m, np) <= max_lds ? np : 0;
 }
 
+static long long var_jac_per(const pcl_ctx *c);
 static long long jac_per_full(const pcl_ctx *c) {
+    if (c->var) return var_jac_per(c);
     return 2LL * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
 static long long jac_per_compact(const pcl_ctx *c) { return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1); }
@@ -303,7 +314,7 @@ static long long z_len(const pcl_ctx *c) {
     return (long long)c->desc.z_dim * c->desc.N * (c->desc.batch_mode == PCL_BATCH_TRAJ ? c->desc.batch : 1);
 }
 static long long n_rows(const pcl_ctx *c) { return (long long)c->win_count * c->x_dim * c->K; }        // of the member window
-static long long n_rows_all(const pcl_ctx *c) { return (long long)c->desc.batch * c->x_dim * c->K; }  // of every member (allocation sizes)
+static long long n_rows_all(const pcl_ctx *c) { return (long long)(c->var ? 1 : c->desc.batch) * c->x_dim * c->K; }  // of every member (allocation sizes)
 
 extern "C" const char *pcl_version(void) { return PCL_VERSION_STR; }
 
@@ -317,6 +328,8 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
     return PCL_OK;
 }
 
+#include "pcl_host_variational.hpp"
+
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (!out) return fail(nullptr, PCL_EINVAL, "pcl_create: out is NULL");
     *out = nullptr;
@@ -324,6 +337,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
+    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL) return var_create(dsc, out);
     const bool vec = dsc->state_cols == PCL_STATE_VECTOR;  // general real d x d generator on one real column
     const int d = dsc->d, m = dsc->n_drives, n = vec ? d : 2 * d;
     if (d < 1 || m < 0 || dsc->N < 2 || dsc->batch < 1)
@@ -612,7 +626,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);
@@ -666,6 +680,7 @@ extern "C" int pcl_jac_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
 }
 extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count) {
     if (!ctx) return PCL_EINVAL;
+    VAR_NOTIMPL(ctx, "pcl_set_member_window");
     if (first < 0 || count < 1 || (long long)first + count > ctx->desc.batch)
         return fail(ctx, PCL_EINVAL, "pcl_set_member_window: [%d, %d) outside the %d members of this context", first, first + count, ctx->desc.batch);
     ctx->win_first = first;
@@ -674,6 +689,7 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 }
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
+    VAR_NOTIMPL(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
     if (nnz) *nnz = jac_per_compact(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
@@ -689,6 +705,7 @@ template <class I>
 static int jac_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_jac_structure: NULL output");
+    if (ctx->var) return var_jac_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
     const long long n = ctx->n, d = ctx->cols, m = D.n_drives, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
     const long long per = jac_per_full(ctx);
@@ -734,6 +751,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
+    if (ctx->var) return var_hess_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
     const long long m = D.n_drives, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
     const long long per = hess_per(ctx);
@@ -1314,6 +1332,10 @@ static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where);
 static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *jac, bool compact) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_eval / pcl_jac")) return rc;
+    if (ctx->var) {
+        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (PCL_BATCH_VARIATIONAL)");
+        return var_launch_fused(ctx, Z, delta, jac);
+    }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
     KParams p;
     fill_params(ctx, p);
@@ -1590,6 +1612,7 @@ static size_t hess2_lds_bytes(const KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
+    if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);
     if (int rc = resolve_order(ctx, nullptr, "pcl_hess")) return rc;
     KParams p;
     fill_params(ctx, p);
@@ -2089,7 +2112,7 @@ extern "C" int pcl_set_order_policy(pcl_ctx *ctx, double dt_max, const double *u
 #ifdef PCL_LAB
     if (ctx->res.active) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: a resident evaluator is running (pcl_resident_stop first)");
 #endif
-    const int n = ctx->n, m = ctx->desc.n_drives;
+    const int n = ctx->var ? ctx->var_nl : ctx->n, m = ctx->desc.n_drives;
     const double theta = policy_theta(n, m, ctx->hG0.data(), ctx->hG0.size() / ((size_t)n * n), ctx->hGj.data(), dt_max, u_max);
     ctx->order_tol = tol;
     bool met = true;
@@ -2104,7 +2127,7 @@ static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where) 
     if (ctx->desc.pade_order != 0) return PCL_OK;
     if (!Z_host) return fail(ctx, PCL_EINVAL, "%s: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first", where);
     const pcl_desc &D = ctx->desc;
-    const int n = ctx->n, m = D.n_drives;
+    const int n = ctx->var ? ctx->var_nl : ctx->n, m = D.n_drives;  // (variational: the lifted generator)
     const int nbuf = D.batch_mode == PCL_BATCH_TRAJ ? D.batch : 1;
     std::vector<double> G((size_t)n * n);
     double theta = 0.0;
@@ -2202,6 +2225,7 @@ extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *d
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
+    VAR_NOTIMPL(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
     const long long n_bk = (long long)ctx->win_count * ctx->K;
     if (ctx->cols == 1) {  // one state column (kets, compact density vectors): the compact layout IS the full layout
@@ -2229,6 +2253,7 @@ extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, dou
 extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
+    VAR_NOTIMPL(ctx, "pcl_rollout_dev");
     ON_DEVICE(ctx);
     KParams p;
     fill_params(ctx, p);
@@ -2299,9 +2324,9 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     ON_DEVICE(ctx);
     TRY(resolve_order(ctx, Z, "pcl_eval_jac"));
     const auto t_begin = std::chrono::steady_clock::now();
-    const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)ctx->desc.batch * ctx->K;
+    const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1;
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var;  // (variational contexts: full values, host_path 1)
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -2390,7 +2415,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
     const long long nv = hess_per(ctx) * ctx->win_count * ctx->K;
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->dmu, n_rows_all(ctx)));
-    TRY(ensure(ctx, &ctx->dhess, hess_per(ctx) * ctx->desc.batch * ctx->K));
+    TRY(ensure(ctx, &ctx->dhess, hess_per(ctx) * (ctx->var ? 1 : ctx->desc.batch) * ctx->K));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dZ, Z, z_len(ctx) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dmu, mu, n_rows(ctx) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TRY(launch_hess(ctx, ctx->dZ, ctx->dmu, ctx->dhess));
@@ -2402,6 +2427,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
 extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout: NULL pointer");
+    VAR_NOTIMPL(ctx, "pcl_rollout");
     ON_DEVICE(ctx);
     const long long nv = (long long)ctx->win_count * ctx->desc.N * ctx->x_dim;
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));

@@ -20,12 +20,13 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PclError
+from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL, PclError
 from .trajectory import STATE, TIMESTEP, NamedTrajectory
 
 __all__ = [
     "HipPadeIntegrator", "HipPadeMemberIntegrator", "HipPadeMultistart", "DerivativeIntegrator", "BilinearIntegrator", "evaluate_", "eval_jacobian",
-    "jacobian_structure", "hessian_structure", "eval_hessian_of_lagrangian", "PclError",
+    "jacobian_structure", "hessian_structure", "eval_hessian_of_lagrangian", "PclError", "HipVariationalIntegrator", "VariationalUnitaryIntegrator",
+    "VariationalKetIntegrator",
 ]  # fmt: skip
 
 
@@ -87,8 +88,11 @@ class _PclContext:
         self.jac_nnz, self.jac_per = a.value, b.value
         self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
         self.hess_nnz, self.hess_per = a.value, b.value
-        self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
-        self.compact_nnz, self.compact_per = a.value, b.value
+        if batch_mode == PCL_BATCH_VARIATIONAL:  # (no compact Jacobian for the stacked state)
+            self.compact_nnz = self.compact_per = 0
+        else:
+            self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
+            self.compact_nnz, self.compact_per = a.value, b.value
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
         self.window = (0, batch)
 
@@ -521,6 +525,92 @@ class HipPadeIntegrator:
         self._ctx.close()
         if self._f_ctx is not None:
             self._f_ctx.close()
+
+
+class HipVariationalIntegrator:
+    """Drop-in for the ``BilinearIntegrator`` the reference's variational constructors build [REF src/control/integrators.jl:234-264]: the state
+    ``vcat(x, x_var_1, ..., x_var_v)`` evolved by ``var_G(G(u), [Gv_i])`` per state column, ``Gv_i = G(H_var_i) / scale_i``.  One context of
+    batch_mode PCL_BATCH_VARIATIONAL; rows are knot-major over the stacked state (``B.dim = B.x_dim * (N - 1)``).  Build it with
+    ``VariationalUnitaryIntegrator`` or ``VariationalKetIntegrator``."""
+
+    def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10):
+        x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
+        names = [x_name] + x_variations
+        n = 2 * sys.levels
+        cols = 1 if ket else sys.levels
+        if not x_variations:
+            raise ValueError("at least one variation component is required")
+        if len(x_variations) != len(Gv):
+            raise ValueError("%d variation components for %d variational generators" % (len(x_variations), len(Gv)))
+        for nm in names + [u_name]:
+            if nm not in traj.components:
+                raise KeyError("trajectory has no component %r" % (nm,))
+        for nm in names:
+            if len(traj.components[nm]) != n * cols:
+                raise ValueError("component %r has dim %d; a %s of %d levels takes %d" % (nm, len(traj.components[nm]), "ket" if ket else "unitary",
+                                                                                        sys.levels, n * cols))  # fmt: skip
+        m = sys.n_drives
+        if m and len(traj.components[u_name]) < m:
+            raise ValueError("drive component %r has dim %d < n_drives = %d" % (u_name, len(traj.components[u_name]), m))
+        self.x_names = names
+        self.x_name = tuple(names)
+        self.u_name = u_name
+        self.G_drift = np.asarray(sys.G_drift, dtype=np.float64)
+        self.G_drives = np.asarray(sys.G_drives_array(), dtype=np.float64).reshape(m, n, n)
+        self.G_vars = np.asarray(Gv, dtype=np.float64).reshape(len(Gv), n, n)
+        self._sig = (traj.dim, traj.N)
+        self._ctx = _PclContext(
+            d=sys.levels, m=m, N=traj.N, z_dim=traj.dim, u_off=traj.components[u_name].start, dt_off=traj.components[traj.timestep].start,
+            x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
+            batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
+            index_base=index_base, pade_order=pade_order, state_cols=cols,
+        )  # fmt: skip
+        if pade_order == 0:
+            _decide_order(self._ctx, traj, u_name, m, order_tol)
+        self.x_dim = self._ctx.x_dim
+        self.dim = self._ctx.n_rows
+
+    @property
+    def ctx(self):
+        return self._ctx
+
+    @property
+    def pade_order(self):
+        return self._ctx.pade_order
+
+    def _check(self, traj):
+        if (traj.dim, traj.N) != self._sig:
+            raise ValueError("trajectory shape (dim=%d, N=%d) differs from the one this integrator was built for %r" % (traj.dim, traj.N, self._sig))
+
+    def close(self):
+        self._ctx.close()
+
+
+def _variational_generators(sys, scales):
+    from .quantum import VariationalQuantumSystem
+
+    if not isinstance(sys, VariationalQuantumSystem):
+        raise TypeError("a VariationalQuantumSystem is required, got %s" % type(sys).__name__)
+    Gv = sys.G_vars_array()
+    scales = np.broadcast_to(np.asarray(scales, dtype=np.float64), (len(Gv),))
+    if np.any(scales == 0):
+        raise ValueError("scales must be non-zero")
+    return [Gv[i] / scales[i] for i in range(len(Gv))]
+
+
+def VariationalUnitaryIntegrator(sys, traj, x_name, x_variations, u_name="u", *, scales=None, **kw):
+    """``VariationalUnitaryIntegrator(sys, traj, :U, [:U_var, ...], :u; scales)`` [REF src/control/integrators.jl:247-264]: generator
+    ``var_G(I (x) G(u), [I (x) G_var_i / scales[i]])`` on ``vcat(U, U_var_1, ...)``; ``scales`` defaults to ones.  Keyword arguments as for
+    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``)."""
+    Gv = _variational_generators(sys, 1.0 if scales is None else scales)
+    return HipVariationalIntegrator(sys, traj, x_name, x_variations, u_name, Gv, ket=False, **kw)
+
+
+def VariationalKetIntegrator(sys, traj, x_name, x_variations, u_name="u", *, scale=1.0, **kw):
+    """``VariationalKetIntegrator(sys, traj, :psi, [:psi_var, ...], :u; scale)`` [REF src/control/integrators.jl:234-245]: generator
+    ``var_G(G(u), [G_var_i / scale])`` on ``vcat(psi, psi_var_1, ...)``."""
+    Gv = _variational_generators(sys, float(scale))
+    return HipVariationalIntegrator(sys, traj, x_name, x_variations, u_name, Gv, ket=True, **kw)
 
 
 class _EnsembleCore:

@@ -244,6 +244,56 @@ function HipPadeIntegrator(qtraj::SamplingTrajectory, N::Int; kwargs...)
 end
 
 # ---- cached fused evaluation -------------------------------------------------------------------------------------
+# ---- variational (sensitivity) integrators: batch_mode PCL_BATCH_VARIATIONAL (= 2) -- ONE context over the stacked state
+#      vcat(x, x_var_1, ...), generator var_G(G(u), [G_var_i / scale_i]); rows knot-major over the stacked state (B.dim = x_dim (N - 1)).
+#      The member window does not exist for this mode: the structure is queried whole.
+function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
+                      device::Integer = 0, pade_order::Integer = 0, order_tol::Float64 = 1e-10)
+    m = sys.n_drives
+    e(j) = (a = zeros(m); a[j] = 1.0; a)
+    zu = zeros(m)
+    G0 = Matrix{Float64}(sys.G(zu))                                   # the variational system's G takes the controls only
+    Gj = [Matrix{Float64}(sys.G(e(j))) - G0 for j in 1:m]
+    Gv = [Matrix{Float64}(Gvf(zu)) ./ s for (Gvf, s) in zip(sys.G_vars, scales)]   # sys.G_vars: functions of the controls [REF variational_quantum_systems.jl:66-124]
+    names = vcat(x, x_vars...)
+    x_offs = Int32[traj.components[nm][1] - 1 for nm in names]
+    G0s = reduce(vcat, [vec(G) for G in vcat([G0], Gv)])
+    Gjv = m == 0 ? zeros(1) : reduce(vcat, [vec(G) for G in Gj])
+    ctx = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve G0s Gjv x_offs begin
+        desc = PclDesc(sizeof(PclDesc), size(G0, 1) ÷ 2, m, traj.N, traj.dim, traj.components[u][1] - 1, traj.components[traj.timestep][1] - 1,
+                       length(names), 2 #= PCL_BATCH_VARIATIONAL =#, pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
+                       state_cols, traj.global_dim, pointer(G0s), pointer(Gjv), pointer(x_offs))
+        rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
+        rc == 0 || error("pcl_create: ", _lasterr(C_NULL))
+    end
+    c = ctx[]
+    xd = Ref{Int64}(0); nr = Ref{Int64}(0); ncol = Ref{Int64}(0); nnz = Ref{Int64}(0); per = Ref{Int64}(0); hnnz = Ref{Int64}(0)
+    check(c, ccall((:pcl_constraint_dim, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), c, xd, nr, ncol))
+    check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
+    finalizer(_destroy!, core)
+    pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
+    order = _order_in_use(core)
+    order == 0 && error("HipPadeIntegrator: the Pade order could not be decided")
+    jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
+    check(c, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, jr, jc))
+    hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
+    check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
+    # (B.f is refused for the stacked state, see _f: fcore stays `nothing`)
+    return HipPadeIntegrator(core, 1, x, names, u, core.x_dim, core.rows_per, jr, jc, hr, hc, Int(ncol[]), G0, Gj, state_cols, order, nothing)
+end
+
+# VariationalKetIntegrator(sys, traj, :ψ̃, [:ψ̃_var, ...], :u; scale)          [REF src/control/integrators.jl:234-245]
+VariationalKetIntegrator(sys, traj::NamedTrajectory, ψ̃::Symbol, ψ̃_variations::AbstractVector{Symbol}, u::Symbol; scale::Float64 = 1.0, kwargs...) =
+    _variational(sys, traj, ψ̃, ψ̃_variations, u, fill(scale, length(sys.G_vars)), 1; kwargs...)
+
+# VariationalUnitaryIntegrator(sys, traj, :Ũ⃗, [:Ũ⃗_var, ...], :u; scales)       [REF src/control/integrators.jl:247-264]
+VariationalUnitaryIntegrator(sys, traj::NamedTrajectory, Ũ⃗::Symbol, Ũ⃗_variations::AbstractVector{Symbol}, u::Symbol;
+                             scales::AbstractVector{<:Float64} = fill(1.0, length(sys.G_vars)), kwargs...) =
+    _variational(sys, traj, Ũ⃗, Ũ⃗_variations, u, Vector{Float64}(scales), 0; kwargs...)
+
 function _fresh!(core::PclCore, z::AbstractVector{Float64})
     if length(core.z) != length(z) || core.z != z
         core.z = copy(z)
@@ -386,6 +436,9 @@ __init__() = _bind_to_directtrajopt!()
 # ---- B.f(x_next, x, u, Δt): the scalar one-interval form the reference reads [REF integrators.jl:518-525,552;
 #      src/control/display/inspect.jl:630-636] -- a cached 2-knot context with layout [x | Δt | u] -----------------------
 function _f(B::HipPadeIntegrator, x_next::AbstractVector, x::AbstractVector, u::AbstractVector, Δt::Real)
+    # a variational integrator (several stacked state names on one context) has no one-interval form here: its generator is the lifted
+    # var_G(G(u), [Gv_i]), which a plain two-knot context of the nominal generators does not evaluate
+    length(getfield(B, :x_names)) > 1 && error("B.f is not available for a variational integrator (stacked state $(getfield(B, :x_names)))")
     xd = getfield(B, :x_dim); Gj = getfield(B, :Gj); m = length(Gj)
     fc = getfield(B, :fcore)
     if fc === nothing
@@ -409,5 +462,5 @@ function Base.getproperty(B::HipPadeIntegrator, s::Symbol)
 end
 Base.propertynames(B::HipPadeIntegrator, private::Bool = false) = (fieldnames(HipPadeIntegrator)..., :f, :ctx)
 
-export HipPadeIntegrator
+export HipPadeIntegrator, VariationalKetIntegrator, VariationalUnitaryIntegrator
 end # module

@@ -21,7 +21,7 @@ __all__ = [
     "ket_to_iso", "iso_to_ket", "operator_to_iso_vec", "iso_vec_to_operator",
     "iso_vec_to_iso_operator", "iso_operator_to_iso_vec", "iso", "G", "H",
     "QuantumSystem", "CompositeQuantumSystem", "TransmonSystem",
-    "TransmonDipoleCoupling", "MultiTransmonSystem",
+    "TransmonDipoleCoupling", "MultiTransmonSystem", "VariationalQuantumSystem",
 ]  # fmt: skip
 
 _c = np.complex128
@@ -164,6 +164,48 @@ class QuantumSystem:
     def G_drives_array(self):
         n = 2 * self.levels
         return np.array(self.G_drives).reshape(self.n_drives, n, n)
+
+
+class VariationalQuantumSystem(QuantumSystem):
+    """A linear-drive system with perturbation directions ``H_vars`` [REF src/quantum/systems/variational_quantum_systems.jl:66-124]: the
+    variational integrators carry the first-order sensitivity of the state to each direction, generated by ``G(H_var)``.
+
+    ``VariationalQuantumSystem(H_drift, H_drives, H_vars, drive_bounds)`` or, without a drift, ``VariationalQuantumSystem(H_drives, H_vars,
+    drive_bounds)``.  ``G_vars[i]`` is a function of the controls as in the reference (here constant: ``a -> G(H_vars[i])``);
+    ``G_vars_array()`` holds the matrices.  The functional form (``H`` and ``H_vars`` given as functions of the controls,
+    variational_quantum_systems.jl:111-124) has no linear-drive structure for the device and raises ``NotImplementedError``."""
+
+    def __init__(self, *args):
+        """``(H_drift, H_drives, H_vars, drive_bounds)`` or ``(H_drives, H_vars, drive_bounds)``: told apart by the arguments' kinds, as the
+        reference's dispatch does (a matrix first: the drift; a list of matrices first: no drift).  Nothing is optional."""
+        if any(callable(a) or (isinstance(a, (list, tuple)) and any(callable(x) for x in a)) for a in args):
+            raise NotImplementedError("the functional form of VariationalQuantumSystem (H and H_vars as functions of the controls) has no "
+                                      "linear-drive generator the device kernels can take; give H_drift, H_drives and H_vars as matrices")
+        is_matrix = lambda a: np.ndim(a) == 2 and not isinstance(a, (list, tuple))
+        is_matrices = lambda a: isinstance(a, (list, tuple, np.ndarray)) and (len(a) == 0 or all(np.ndim(x) == 2 for x in a)) and np.ndim(a) != 2
+        if len(args) == 4 and is_matrix(args[0]) and is_matrices(args[1]) and is_matrices(args[2]):
+            H_drift, H_drives, H_vars, drive_bounds = args
+        elif len(args) == 3 and is_matrices(args[0]) and is_matrices(args[1]) and not is_matrices(args[2]):
+            H_drives, H_vars, drive_bounds = args
+            if len(H_drives) == 0:
+                raise AssertionError("At least one drive is required")
+            H_drift = None
+        else:
+            raise TypeError("VariationalQuantumSystem takes (H_drift, H_drives, H_vars, drive_bounds) or (H_drives, H_vars, drive_bounds); got %d "
+                            "argument(s) of kinds %s" % (len(args), [type(a).__name__ for a in args]))
+        if H_vars is None or len(H_vars) == 0:
+            raise AssertionError("At least one variational operator is required")
+        super().__init__(H_drift, list(H_drives), drive_bounds)
+        self.H_vars = [np.asarray(Hv, _c) for Hv in H_vars]
+        for Hv in self.H_vars:
+            if Hv.shape != self.H_drift.shape:
+                raise ValueError("H_vars must have the shape of H_drift %r; got %r" % (self.H_drift.shape, Hv.shape))
+        self._G_vars = [G(Hv) for Hv in self.H_vars]
+        self.G_vars = [(lambda a, _g=g: _g.copy()) for g in self._G_vars]
+
+    def G_vars_array(self):
+        n = 2 * self.levels
+        return np.array(self._G_vars).reshape(len(self._G_vars), n, n)
 
 
 class CompositeQuantumSystem(QuantumSystem):
