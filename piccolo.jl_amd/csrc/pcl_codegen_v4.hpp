@@ -25,6 +25,7 @@ constexpr int kV4Chunk = 8;    // drift coefficients per scalar-load chunk (one 
 constexpr int kV4MaxCf = 16;   // resident drive coefficients (drive, magnitude) the product keeps in scalar registers
 constexpr int kV4MaxRes = 28;  // resident coefficients in all (scalar register pairs): the drives' first, then the drift's value classes by use
 constexpr int kV4MaxResStreamed = 16;  // ... when some drift classes do not fit and the rest is streamed (the chunks take 32 scalar registers)
+constexpr int kHcMaxMags = 7;  // column-group Hessian kernel: 10-bit entries of its gathers' table, 1 + 2 magnitudes <= 16 coefficient slots
 
 struct V4Term {
     int row;    // output row inside the half (0 .. d-1)

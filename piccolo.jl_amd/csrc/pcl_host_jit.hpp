@@ -268,7 +268,9 @@ hipFunction_t jit_compile(int device, const std::string &key_, const std::string
         if (it->second.failed) return nullptr;
         if (!plain_name) return it->second.fn;
         hipFunction_t f = nullptr;  // several kernels of one generated module
-        return hipModuleGetFunction(&f, it->second.mod, name_expr) == hipSuccess ? f : nullptr;
+        if (hipModuleGetFunction(&f, it->second.mod, name_expr) == hipSuccess) return f;
+        (void)hipGetLastError();  // (a kernel the module does not hold -- the pair kernel beyond its 16-bit LDS offsets: not an error of the next launch)
+        return nullptr;
     }
     JitKernel &jk = g_jit[key];
     jk.failed = true;
@@ -473,7 +475,7 @@ extern "C" int pcl_jit_prebuild(int d, int m, const double *G0, int n_g0, const 
 extern "C" int pcl_codegen_source_v4(int d, int m, const double *G0, int n_g0, const double *Gj, int q, int what, char *buf, int64_t cap, int64_t *needed) {
     if (d < 1 || d > 32 || m < 0 || m > 6 || n_g0 < 1 || q < 1 || q > 5 || (what != 0 && what != 1 && what != 5) || !G0 || (m > 0 && !Gj) || !needed) return PCL_EINVAL;
     const pcl_codegen::V4Plan plan = pcl_codegen::make_v4_plan(d, m, G0, n_g0, Gj);
-    if (!plan.ok) return PCL_ESHAPE;
+    if (!plan.ok || (what == 5 && plan.mags.size() > (size_t)pcl_codegen::kHcMaxMags)) return PCL_ESHAPE;
     const int np = v4_power_tiles(d, m, q, 160 * 1024);
     if (!np) return PCL_ESHAPE;
     const std::string src = what == 5 ? v4_hess_cols_source(plan, q) : what == 1 ? v4_hess_source(plan, q) : v4_source(plan, q, np);

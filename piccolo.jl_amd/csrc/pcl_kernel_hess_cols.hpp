@@ -490,6 +490,9 @@ extern "C" __global__ __attribute__((amdgpu_flat_work_group_size(64, 64), amdgpu
 #define HP_NBUF 3  // buffers of chain slots between the two waves (2: the chain wave waits for the other one at every level: 27.6 us at order 10; 3: see profiles/r06_hess_pair_*.log)
 #endif
 #define HP_LDS_DOUBLES (HP_NBUF * HP_SLOTS + (2 + HC_NR) * HC_CPW * SP4CS + HC_NCFT + HC_GT_DOUBLES + 2)
+// The pair kernel addresses its LDS with 16-bit offsets: where its LDS is larger (d = 32 from order 8 on) the module holds the one-wave kernel
+// alone, and the host finds no pair kernel in it (launch_hess: pair only with v4_fhessp).
+#if HP_LDS_DOUBLES * 8 < 65536
 static __device__ __forceinline__ void hp_wait(int *w, int target) {  // bounded: a logic error must not hang the device (the caller's values are then wrong: the launch's error word is set)
     for (int it = 0; it < (1 << 22); ++it) {
         if (__hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= target) return;
@@ -715,3 +718,4 @@ extern "C" __global__ __attribute__((amdgpu_flat_work_group_size(128, 128), amdg
 #include "pcl_kernel_hess_cols_parts.hpp"
 #undef HC_PART_TAIL
 }
+#endif  // HP_LDS_DOUBLES * 8 < 65536

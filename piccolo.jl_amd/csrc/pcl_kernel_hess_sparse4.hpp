@@ -183,7 +183,7 @@ extern "C" __global__ __launch_bounds__(64 * SH_NW) void pcl_hess_sparse4_kernel
 #pragma unroll
                 for (int i = 0; i < SPD; ++i) Rt[own + i] = r[i];
             };
-            double hp = 1.0;                      // h^(j-1)
+            double hp = 1.0, hm = 0.0;            // h^(j-1), h^(j-2): both multiplied up (hp / h is 0/0 at a step of zero)
 #pragma unroll 1
             for (int j = 1; j <= q; ++j) {
                 if (wave > 0) {  // V_{l,j} = G^T V_{l,j-1} + G_l^T W_{j-1}
@@ -253,7 +253,7 @@ extern "C" __global__ __launch_bounds__(64 * SH_NW) void pcl_hess_sparse4_kernel
                     }
                     const double dy = sg * (dot0 + dot1);  // <chain_j, Y_j>
                     if (wave == 0) {
-                        if (j >= 2) s_y = __builtin_fma(j * (j - 1) * cj * (hp / h), dy, s_y);  // T''_j = j (j-1) c_j h^(j-2)
+                        if (j >= 2) s_y = __builtin_fma(j * (j - 1) * cj * hm, dy, s_y);  // T''_j = j (j-1) c_j h^(j-2)
                     } else {
                         s_y = __builtin_fma(T1, dy, s_y);
                         // (u,u): <V_{l,j}, G_i R_j>, every drive i
@@ -266,6 +266,7 @@ extern "C" __global__ __launch_bounds__(64 * SH_NW) void pcl_hess_sparse4_kernel
                     }
                 }
                 SH_STAMP();
+                hm = hp;
                 hp *= h;
             }
 #if SH_SPLIT > 1

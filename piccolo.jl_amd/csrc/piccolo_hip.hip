@@ -1110,7 +1110,12 @@ static int launch_eval_v4(pcl_ctx *ctx, KParams &p) {
     // small launches (up to two intervals per CU: a line-search trial on one to four trajectories): four waves per interval, the products in
     // four row ranges -- config 3, one trajectory: 8.7 -> 6.3 us per launch at order 4, 11.9 -> 7.8 at order 8; four trajectories 9.1 -> 7.9;
     // eight: 10.0 -> 11.8, so one wave per interval above (option eval_coop: -1 auto | 0 | 1)
-    const bool coop = ctx->v4_fevalc && (ctx->opt_eval_coop == 1 || (ctx->opt_eval_coop < 0 && items <= 2LL * std::max(ctx->n_cu, 1)));
+    // (one wave per interval holds three tiles per wave, 12 in all: more than the LDS from d = 29 on -- the cooperative kernel's four tiles take those systems)
+    const bool fits1 = lds <= (size_t)ctx->max_lds;
+    if (!fits1 && ctx->opt_eval_coop == 0)
+        return fail(ctx, PCL_ESHAPE, "eval_coop=0: one wave per interval needs %zu bytes of LDS at d = %d, the device has %zu", lds, p.d, (size_t)ctx->max_lds);
+    const bool coop = ctx->v4_fevalc && (ctx->opt_eval_coop == 1 || !fits1 || (ctx->opt_eval_coop < 0 && items <= 2LL * std::max(ctx->n_cu, 1)));
+    if (!coop && !fits1) return PCL_ENOTIMPL;
     ctx->last_eval_coop = coop ? 1 : 0;
     if (coop) {
         const size_t ldsc = (size_t)4 * p.d * (p.n + 1) * sizeof(double);
@@ -1627,7 +1632,8 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
     //  trajectory, i.e. at most n_cu / 2 intervals: 18.4 against 20.0 us -- kernel 6 needs its value-table launch first)
     const bool cols_auto = ctx->opt_hess_kernel == 0 && !ctx->opt_general &&
                            (ctx->desc.pade_order != 4 || 2LL * p.batch * p.K <= std::max(ctx->n_cu, 1));
-    if ((ctx->opt_hess_kernel == 8 || cols_auto) && v4_available(ctx) && !ctx->v4_hessc_failed && p.m >= 1) {
+    const bool cols_ok = v4_available(ctx) && ctx->v4_plan->mags.size() <= (size_t)pcl_codegen::kHcMaxMags;  // (8 magnitudes: kernel 7 takes them)
+    if ((ctx->opt_hess_kernel == 8 || cols_auto) && cols_ok && !ctx->v4_hessc_failed && p.m >= 1) {
         const pcl_codegen::V4Plan &v4 = *ctx->v4_plan;
         fill_pade(p, ctx->desc.pade_order);
         const long long items = (long long)p.batch * p.K;
@@ -1732,7 +1738,8 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
         }
         if (ctx->opt_hess_kernel == 8) return fail(ctx, PCL_ESHAPE, "hess_kernel=8: the column-group kernel is not available (%s)", g_jit_note.c_str());
     } else if (ctx->opt_hess_kernel == 8) {
-        return fail(ctx, PCL_ESHAPE, "hess_kernel=8 needs sparse exact-iso generators of a unitary problem (9 <= d <= 32), 1..6 drives and jit=1");
+        return fail(ctx, PCL_ESHAPE, "hess_kernel=8 needs sparse exact-iso generators of a unitary problem (9 <= d <= 32), 1..6 drives, at most %d distinct drive magnitudes and jit=1",
+                    pcl_codegen::kHcMaxMags);
     }
     // hess_kernel 7 (auto where kernel 8 is not available): the pattern-compiled kernel on the products of fused kernel 4 -- any order,
     // one workgroup of m + 1 waves per interval (column slices where the m + 3 + 2 (q - 2) tiles do not fit LDS)

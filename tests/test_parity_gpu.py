@@ -16,6 +16,8 @@ import piccolo_jl_amd as pa
 from helpers import ref_case, traj_from_Z
 from oracle import pade_oracle as po
 from oracle import ref_lib
+from shape_cases import random_case as _random_case
+from shape_cases import random_sparse_iso_system as _random_sparse_iso_system
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
@@ -426,18 +428,6 @@ def test_multistart_batch_matches_single():
 
 
 # ---- edge cases ------------------------------------------------------------------------------------------
-def _random_case(d, m, N, rng, x_off=0, pad=3):
-    n = 2 * d
-    xd = 2 * d * d
-    z_dim = x_off + xd + pad + m + 1
-    lay = po.Layout(d=d, m=m, N=N, z_dim=z_dim, x_off=x_off, u_off=x_off + xd + 1, dt_off=x_off + xd)
-    G0 = rng.standard_normal((n, n))
-    Gj = rng.standard_normal((m, n, n)) * (rng.random((m, n, n)) < 0.3) if m else np.zeros((0, n, n))
-    Z = rng.standard_normal((N, z_dim))
-    Z[:, lay.dt_off] = 0.05 + 0.1 * rng.random(N)
-    return lay, G0, Gj, Z
-
-
 @pytest.mark.parametrize(
     "d,m,N,x_off",
     [(1, 1, 2, 0), (1, 0, 3, 0), (2, 0, 4, 0), (3, 2, 2, 5), (4, 7, 3, 1), (8, 1, 3, 0), (16, 2, 3, 0), (27, 6, 2, 3), (32, 3, 2, 0)],
@@ -2798,34 +2788,6 @@ def test_column_group_hessian_kernel(order):
             assert np.array_equal(hb.reshape(-1), cb.hess(np.stack(Zs), mus.reshape(-1)))
         cb.close()
         c1.close()
-
-
-def _random_sparse_iso_system(d, m, rng, n_mags=3):
-    """Sparse Hermitian drift and drives (complex entries: the A and the B block of iso(-iH) are both populated), drive
-    entries drawn from a few magnitudes with random signs / phases in {1, i}: what the pattern-compiled kernels specialise on."""
-    def herm(mask_density, vals):
-        H = np.zeros((d, d), dtype=complex)
-        for i in range(d):
-            for j in range(i, d):
-                if rng.random() < mask_density:
-                    v = vals()
-                    if i == j:
-                        H[i, i] = v.real if v.real != 0 else abs(v)
-                    else:
-                        H[i, j] = v
-                        H[j, i] = np.conj(v)
-        return H
-    density = min(0.18, 2.5 / d)  # (a few hundred entries in the union pattern at every size)
-    H0 = herm(density, lambda: complex(rng.standard_normal(), rng.standard_normal()))
-    H0 += np.diag(rng.standard_normal(d))
-    mags = [1.0, np.sqrt(2.0), 0.37][:n_mags]
-    Hd = [herm(density * 0.5, lambda: rng.choice(mags) * rng.choice([1.0, -1.0]) * rng.choice([1.0, 1j])) for _ in range(m)]
-    for H in Hd:  # every drive has entries in both blocks
-        i, j = rng.choice(d, 2, replace=False)
-        H[i, j] += 1j * mags[0]
-        H[j, i] -= 1j * mags[0]
-        H[i, i] += mags[0]
-    return po.G_of_H(H0), np.array([po.G_of_H(H) for H in Hd])
 
 
 @pytest.mark.parametrize("d,m,Bn,N", [(9, 1, 2, 4), (12, 2, 1, 5), (13, 6, 2, 3), (20, 3, 3, 4), (31, 5, 1, 3), (32, 4, 2, 3)])

@@ -148,9 +148,11 @@ def h_var_drift(levels_per, n_sub):
     return 2 * np.pi * H
 
 
-def make_case(sys_o, Gv, N, seed, ket=False, dt=0.1, u_scale=0.02, noise=1e-3, extra=0):
+def make_case(sys_o, Gv, N, seed, ket=False, dt=0.1, u_scale=0.02, noise=1e-3, extra=0, xo=None, u_off=None, dt_off=None, t_off=None,
+              z_dim=None):
     """A trajectory [X | Xv_1 .. Xv_v | dt | t | u | (extra zeros)] near the exact propagation of the lifted system (so delta is small
-    but not zero)."""
+    but not zero).  Any other knot: the offsets of the 1 + v components (xo), of the controls, of dt and of t, and z_dim, all given;
+    m = 0 (drift only) too."""
     import scipy.linalg
 
     rng = np.random.default_rng(seed)
@@ -158,16 +160,21 @@ def make_case(sys_o, Gv, N, seed, ket=False, dt=0.1, u_scale=0.02, noise=1e-3, e
     n, C = 2 * d, (1 if ket else d)
     v = len(Gv)
     xdc = n * C
-    xo = [b * xdc for b in range(v + 1)]
-    dt_off = (v + 1) * xdc
-    u_off = dt_off + 2
-    z_dim = u_off + m + extra
+    if xo is None:
+        xo = [b * xdc for b in range(v + 1)]
+        dt_off = (v + 1) * xdc
+        t_off = dt_off + 1
+        u_off = dt_off + 2
+        z_dim = u_off + m + extra
+    assert len(xo) == v + 1 and None not in (u_off, dt_off, z_dim)
     Z = np.zeros((N, z_dim))
     u = np.clip(u_scale * rng.standard_normal((N, m)), -0.1, 0.1)
     Z[:, dt_off] = dt * (1 + 0.1 * rng.random(N))
-    Z[:, dt_off + 1] = np.cumsum(Z[:, dt_off])
+    if t_off is not None:
+        Z[:, t_off] = np.cumsum(Z[:, dt_off])
     Z[:, u_off : u_off + m] = u
     G0, Gj = np.asarray(sys_o.G_drift), np.array(sys_o.G_drives).reshape(m, n, n)
+    xo = list(xo)
     X0 = np.vstack([np.eye(d), np.zeros((d, d))])[:, :C]
     S = np.concatenate([X0] + [0.01 * rng.standard_normal((n, C)) for _ in range(v)], axis=0)  # [n', C]
     for k in range(N):
