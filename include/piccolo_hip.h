@@ -106,7 +106,15 @@ typedef enum pcl_status {
                                -- (2 + 4v) C n^2 + x_dim (m+1) values, no structural zeros.  Hessian: the segments below over the stacked
                                state.  Entry points: create, dimensions, structures, pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev],
                                pcl_hess[_dev] (host-pointer calls deliver full values), the order policy (theta of the lifted generator),
-                               streams, options, pcl_deriv_*; every other entry point returns PCL_ENOTIMPL. */
+                               streams, options, pcl_deriv_*; every other entry point returns PCL_ENOTIMPL -- unless the context's option
+                               "var_full" is set to 1 (pcl_set_option; default 0).  Then the robust-control objective and the rollout are
+                               served as well: pcl_set_goal, pcl_set_goal_subspace (unitary), pcl_set_goal_form with scope 0 (the loss of
+                               component 0, the state itself; A is R x (n C); scope 1 stays PCL_ENOTIMPL), pcl_add_regularizer /
+                               pcl_clear_regularizers (any component of the knot), pcl_set_weights, pcl_objective[_dev],
+                               pcl_objective_hess_nnz / _structure / [_dev] and pcl_rollout[_dev]; see their comments.  Setting the option
+                               back to 0 restores the refusals and drops goal, weights and regularisers.  pcl_infidelity_dev, the merit /
+                               reduce entry points, the member window and the compact Jacobian stay PCL_ENOTIMPL whatever the option says.
+                               The sensitivity term is evaluated at the TERMINAL knot only (the reference's own use, materialize.jl:306-307). */
 
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
@@ -228,14 +236,21 @@ int pcl_deriv_eval_jac_dev(pcl_ctx *ctx, int32_t x_off, int32_t dx_off, int32_t 
  *   QuadraticRegularizer(name, traj, R) x3 [EXT DirectTrajOpt]                              src/control/templates/smooth_pulse_problem.jl:249-251
  * pcl_set_goal copies the goal's iso-vec (x_dim doubles, operator_to_iso_vec(U_goal)); pcl_set_goal_subspace the iso-vec of
  * the ns x ns block unembed(op) (2 ns^2 doubles) and its ns 0-based subspace indices (op.subspace - 1); the later call wins.
- * pcl_set_weights: per member / seed weights w (batch doubles, NULL = ones).
+ * pcl_set_weights: per member / seed weights w (batch doubles, NULL = ones).  On a variational context (option var_full) w has batch = 1 + v
+ * entries: w[0] multiplies the terminal infidelity of the state, w[i] (i = 1..v) is the coefficient of the sensitivity loss of variation i at the
+ * terminal knot -- UnitarySensitivityObjective, src/control/objectives.jl:437-453: scale^4 abs2(tr(U'U)) / n^2 = (|x|^2)^2 / d^2 for the iso-vec x,
+ * with Qs and scale^4 folded into w[i] by the binding.  NULL = [1, 0, .., 0]: no sensitivity term.  A negative or non-finite entry is PCL_EINVAL;
+ * a non-zero w[i >= 1] on a ket context is PCL_ENOTIMPL (the reference has no ket sensitivity objective).
  * pcl_infidelity_dev writes one value per member / seed (value_dev[batch]) and the gradient w.r.t. that member's terminal
  * state (grad_dev[batch*x_dim], iso-vec order); either output may be NULL.
  * Regularisers: J_r = 1/2 sum_k dt_k^p sum_i R_i Z[k, off+i]^2 with p = dt_power in {0, 1, 2}.  DirectTrajOpt is not vendored
  * with the reference and nothing in the reference pins the value; p = 2 (r_k = dt_k v_k, J += r_k' R r_k / 2) is the form of
  * its QuantumCollocation lineage, p = 0 the plain knot-point form -- the binding chooses.
  * pcl_objective[_dev]: the whole objective and its gradient w.r.t. the variable vector.  MEMBERS mode: value[1] = sum over
- * members + regularisers, grad[z_dim*N].  TRAJ mode: value[batch], grad[batch][z_dim*N] (one NLP per seed).  grad may be NULL. */
+ * members + regularisers, grad[z_dim*N].  TRAJ mode: value[batch], grad[batch][z_dim*N] (one NLP per seed).  grad may be NULL.
+ * Variational context (option var_full): value[1], grad[z_dim*N] of
+ *     J = Q w0 |1 - F(X_N)| + sum_i w_i (|Xv_i,N|_F^2)^2 / d^2 + regularisers
+ * (no goal: no infidelity term; no goal, no non-zero w_i and no regulariser: PCL_EINVAL), always ONE launch ("last_objective_launches"). */
 int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec);
 int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns);
 int pcl_set_weights(pcl_ctx *ctx, const double *weights);
@@ -261,7 +276,11 @@ int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, c
  * src/control/templates/spline_pulse_problem.jl:96).  Terminal loss (any goal above, pcl_set_goal and pcl_set_goal_subspace included): per
  * term the lower triangle of -s w Q sigma (2 sum_r A_r A_r'), s = sign(1 - F) -- the Gram triangle is formed once per goal, an evaluation
  * is a scaled copy.  Regularisers: d2/dv_i^2 = dt^p R_i, d2/ddt dv_i = p dt^(p-1) R_i v_i, d2/ddt^2 = p (p - 1) / 2 dt^(p-2) sum_i R_i v_i^2.
- * Each entry once as (max index, min index); the order is reported by pcl_objective_hess_structure (index_base as in pcl_desc). */
+ * Each entry once as (max index, min index); the order is reported by pcl_objective_hess_structure (index_base as in pcl_desc).
+ * Variational context (option var_full): the Gram triangle of component 0, then per variation with w_i != 0 the dense lower triangle over
+ * its terminal iso-vec, sigma w_i (4 |x|^2 I + 8 x x') / d^2, then the regularisers' entries.  The structure depends on which w_i are non-zero
+ * and on the regularisers: query nnz and structure AFTER pcl_set_weights / pcl_add_regularizer.  Where a regulariser covers a component that has
+ * a triangle, its terminal-knot diagonal entries are part of that triangle (each position still once). */
 int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz);
 int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols);
 int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z_dev, double Q, double sigma, double *vals_dev);
@@ -293,7 +312,10 @@ int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z_dev, const do
  *   unitary_rollout(traj, sys; interpolation = :constant)                       src/quantum/dynamics.jl:631-667
  *   RolloutStates: "a GPU rollout overwrites `states` in place"                 src/quantum/trajectories/ensemble_trajectory.jl:56-71
  * Exact piecewise-constant propagation X_{k+1} = exp(dt_k G(u_k)) X_k from the knot-0 state of every member / trajectory
- * (scaling and squaring, to rounding).  X_out: [batch][N][x_dim] doubles, iso-vec per knot (knot 0 = the input state). */
+ * (scaling and squaring, to rounding).  X_out: [batch][N][x_dim] doubles, iso-vec per knot (knot 0 = the input state).
+ * Variational context (option var_full): X_out is [N][x_dim] with the stacked x_dim = (1 + v) n C, components in the order of x_offs, propagated
+ * exactly under the lifted generator: X <- E X, Xv_i <- E Xv_i + L_i X with E = exp(h G) and L_i the Frechet derivative of exp at h G along
+ * h Gv_i (the lifted matrix is never formed); every shape pcl_create accepts.  Component 0 has the bits of a plain context's rollout. */
 int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out);
 int pcl_rollout_dev(pcl_ctx *ctx, const double *Z_dev, double *X_out_dev);
 
@@ -319,6 +341,8 @@ int pcl_comm_destroy(pcl_ctx *ctx);
  *   "host_threads"  threads that expand the compact values into the caller's array in the host-pointer entry points (0 = min(cores / 2, 32);
  *                   -1 = a sweep over the context's first twelve calls), "host_path" (0 auto | 1 full values over PCIe | 2 compact + host expansion)
  *   "v4_ticket"     launches of several trajectories: -1 auto | 0 static split | 1 groups of workgroups + slice tickets
+ *   "var_full"      variational contexts only (1 on any other context: PCL_EINVAL): 1 serves the objective entry points and the rollout
+ *                   (see PCL_BATCH_VARIATIONAL); 0 (default) refuses them and drops goal, weights and regularisers
  * and reads: "pade_order" (the order in use), "last_kernel" / "last_hess_kernel" (which kernel family ran), "jit_compiles", "jit_cache_hits",
  * "jit_fallbacks", "n_cu".  Unknown keys return PCL_EINVAL.  Environment: PCL_JIT_CACHE=0, PCL_JIT_CACHE_DIR, PCL_HOST_PATH, PCL_V4_TICKET,
  * PCL_VERBOSE (see OPTIONS.md). */

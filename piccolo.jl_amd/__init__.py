@@ -22,9 +22,10 @@ from .integrators import (
     jacobian_structure,
     unitary_rollout,
     unitary_rollout_fidelity,
+    variational_rollout,
 )
 from .objectives import (CoherentKetInfidelityObjective, DensityMatrixInfidelityObjective, DensityMatrixPureStateInfidelityObjective, EmbeddedOperator,
-                         KetInfidelityObjective, Objective, QuadraticRegularizer, UnitaryInfidelityObjective, get_subspace_indices)
+                         KetInfidelityObjective, Objective, QuadraticRegularizer, UnitaryInfidelityObjective, UnitarySensitivityObjective, get_subspace_indices)
 from .quantum import (
     GATES,
     PAULIS,

@@ -82,7 +82,7 @@ static int objective_unitary_only(const pcl_ctx *ctx, const char *who) {
 }
 // (re)place the general form of the terminal loss; the Gram triangle of the Hessian is formed at the first Hessian call
 static int set_form(pcl_ctx *ctx, int scope, int R, const double *A, const double *c, bool user) {
-    const long long L = scope ? (long long)ctx->desc.batch * ctx->x_dim : ctx->x_dim;
+    const long long L = ctx->var ? ctx->var_xdc : scope ? (long long)ctx->desc.batch * ctx->x_dim : ctx->x_dim;  // (variational: component 0)
     for (double **q : {&ctx->dformA, &ctx->dformc, &ctx->dgram, &ctx->dcoef}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
@@ -109,19 +109,20 @@ static int set_form(pcl_ctx *ctx, int scope, int R, const double *A, const doubl
 // F = |tr(G'U)|^2 / d^2 = (a'x)^2 + (b'x)^2 with a = iso_vec(G) / d, b = iso_vec(iG) / d   (objectives.jl:330-337)
 static int unitary_form(pcl_ctx *ctx, const double *g) {
     const int d = ctx->desc.d, n = ctx->n;
-    std::vector<double> A((size_t)2 * ctx->x_dim);
+    const long long x_dim = (long long)n * d;
+    std::vector<double> A((size_t)2 * x_dim);
     for (int c = 0; c < d; ++c)
         for (int i = 0; i < d; ++i) {
             const double gr = g[c * n + i], gi = g[c * n + d + i];
             A[c * n + i] = gr / d, A[c * n + d + i] = gi / d;
-            A[ctx->x_dim + c * n + i] = -gi / d, A[ctx->x_dim + c * n + d + i] = gr / d;
+            A[x_dim + c * n + i] = -gi / d, A[x_dim + c * n + d + i] = gr / d;
         }
     return set_form(ctx, 0, 2, A.data(), nullptr, false);
 }
 // F = (|M|_F^2 + |tr M|^2) / (ns (ns + 1)), M = G_s' U[sub, sub]: a row pair per entry of M and one for the trace   (objectives.jl:339-345)
 static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int ns) {
     const int d = ctx->desc.d, n = ctx->n;
-    const long long L = ctx->x_dim;
+    const long long L = (long long)n * d;
     const int R = 2 * ns * ns + 2;
     std::vector<double> A((size_t)R * L, 0.0);
     const double sc = 1.0 / std::sqrt((double)ns * (ns + 1));
@@ -140,7 +141,8 @@ static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int
     return set_form(ctx, 0, R, A.data(), nullptr, false);
 }
 extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c) {
-    VAR_NOTIMPL(ctx, "pcl_set_goal_form");
+    VAR_GATE(ctx, "pcl_set_goal_form");
+    if (ctx && ctx->var) return var_set_goal_form(ctx, scope, R, A, c);
     if (!ctx) return PCL_EINVAL;
     if (scope != 0 && scope != 1) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: scope must be 0 (per member) or 1 (joint)");
     if (scope == 1 && ctx->desc.batch_mode != PCL_BATCH_MEMBERS) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: a joint term needs the members of ONE trajectory buffer");
@@ -153,7 +155,8 @@ extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const d
     return set_form(ctx, scope, R, A, c, true);
 }
 extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
-    VAR_NOTIMPL(ctx, "pcl_set_goal");
+    VAR_GATE(ctx, "pcl_set_goal");
+    if (ctx && ctx->var) return var_set_goal(ctx, goal_iso_vec);
     if (!ctx) return PCL_EINVAL;
     if (!goal_iso_vec) return fail(ctx, PCL_EINVAL, "pcl_set_goal: NULL");
     TRY(objective_unitary_only(ctx, "pcl_set_goal"));
@@ -168,7 +171,8 @@ extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
     return unitary_form(ctx, goal_iso_vec);
 }
 extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns) {
-    VAR_NOTIMPL(ctx, "pcl_set_goal_subspace");
+    VAR_GATE(ctx, "pcl_set_goal_subspace");
+    if (ctx && ctx->var) return var_set_goal_subspace(ctx, goal_sub_iso_vec, subspace, ns);
     if (!ctx) return PCL_EINVAL;
     if (!goal_sub_iso_vec || !subspace) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: NULL");
     TRY(objective_unitary_only(ctx, "pcl_set_goal_subspace"));
@@ -194,7 +198,8 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
 }
 extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
-    VAR_NOTIMPL(ctx, "pcl_set_weights");
+    VAR_GATE(ctx, "pcl_set_weights");
+    if (ctx && ctx->var) return var_set_weights(ctx, w);
     if (!ctx) return PCL_EINVAL;
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -209,7 +214,7 @@ extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
     return PCL_OK;
 }
 extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const double *R, int32_t dt_power) {
-    VAR_NOTIMPL(ctx, "pcl_add_regularizer");
+    VAR_GATE(ctx, "pcl_add_regularizer");
     if (!ctx) return PCL_EINVAL;
     if (!R || dim < 1 || off < 0 || off + dim > ctx->desc.z_dim) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: component [%d, %d) outside the knot (z_dim=%d)", off, off + dim, ctx->desc.z_dim);
     if (dt_power < 0 || dt_power > 2) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: dt_power must be 0, 1 or 2");
@@ -221,7 +226,7 @@ extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const
     return PCL_OK;
 }
 extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
-    VAR_NOTIMPL(ctx, "pcl_clear_regularizers");
+    VAR_GATE(ctx, "pcl_clear_regularizers");
     if (!ctx) return PCL_EINVAL;
     ctx->regs.clear();
     ctx->reg_R.clear();
@@ -277,7 +282,8 @@ static int objective_prepare(pcl_ctx *ctx) {
 static bool tail_applies(const pcl_ctx *ctx, const double *grad, int &lo_, int &hi_);
 static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad, int skip_lo, int skip_hi, double *merit_out);
 extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    VAR_NOTIMPL(ctx, "pcl_objective_dev");
+    VAR_GATE(ctx, "pcl_objective_dev");
+    if (ctx && ctx->var) return var_objective_dev(ctx, Z, Q, value, grad);
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective_dev: NULL pointer");
     if (!ctx->dgoal && !ctx->form_user && ctx->regs.empty()) return fail(ctx, PCL_EINVAL, "pcl_objective_dev: no goal and no regulariser set");
@@ -334,7 +340,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
     return PCL_OK;
 }
 extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    VAR_NOTIMPL(ctx, "pcl_objective");
+    VAR_GATE(ctx, "pcl_objective");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective: NULL pointer");
     ON_DEVICE(ctx);
@@ -422,14 +428,16 @@ static long long obj_hess_per_knot(const pcl_ctx *ctx) {
     return n;
 }
 extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
-    VAR_NOTIMPL(ctx, "pcl_objective_hess_nnz");
+    VAR_GATE(ctx, "pcl_objective_hess_nnz");
+    if (ctx && ctx->var) return var_objective_hess_nnz(ctx, nnz);
     if (!ctx || !nnz) return PCL_EINVAL;
     const int nbuf = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;
     *nnz = obj_hess_terms(ctx) * obj_hess_tri(ctx) + (long long)nbuf * ctx->desc.N * obj_hess_per_knot(ctx);
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols) {
-    VAR_NOTIMPL(ctx, "pcl_objective_hess_structure");
+    VAR_GATE(ctx, "pcl_objective_hess_structure");
+    if (ctx && ctx->var) return var_objective_hess_structure(ctx, rows, cols);
     if (!ctx || !rows || !cols) return PCL_EINVAL;
     const pcl_desc &D = ctx->desc;
     const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
@@ -462,7 +470,8 @@ extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, i
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    VAR_NOTIMPL(ctx, "pcl_objective_hess_dev");
+    VAR_GATE(ctx, "pcl_objective_hess_dev");
+    if (ctx && ctx->var) return var_objective_hess_dev(ctx, Z, Q, sigma, vals);
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess_dev: NULL pointer");
     ON_DEVICE(ctx);
@@ -496,7 +505,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    VAR_NOTIMPL(ctx, "pcl_objective_hess");
+    VAR_GATE(ctx, "pcl_objective_hess");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess: NULL pointer");
     ON_DEVICE(ctx);

@@ -19,6 +19,9 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v < 0) return fail(ctx, PCL_EINVAL, "%s must be >= 0", key);
         (key[4] == 'b' ? ctx->opt_var_blocks : ctx->opt_var_cols) = v;
     }
+    else if (!strcmp(key, "var_full")) {  // variational contexts: serve the objective and the rollout (0: refuse them, and drop goal, weights, regularisers)
+        TRY(var_set_full(ctx, v));
+    }
 #ifdef PCL_PROFILE
     else if (!strcmp(key, "profile_flags"))  // profiling experiments (results may be WRONG); not present in the shipped library
         ctx->opt_prof = v;
@@ -152,6 +155,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->var ? var_split_cols(ctx) : ctx->opt_var_cols;
     else if (!strcmp(key, "variations"))
         *v = ctx->var;
+    else if (!strcmp(key, "var_full"))
+        *v = ctx->var_full;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

@@ -3,6 +3,7 @@
 // validation, structures, and the launches of pcl_kernel_variational.hpp.
 #pragma once
 #include "pcl_kernel_variational.hpp"
+#include "pcl_kernel_var_rollout.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 static long long var_jac_per(const pcl_ctx *c) {
@@ -404,3 +405,18 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
     do {                                                                                                                               \
         if ((ctx) && (ctx)->var) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (PCL_BATCH_VARIATIONAL)", what); \
     } while (0)
+// The objective and the rollout: refused in the same words unless the context's option var_full is on (pcl_host_robust.hpp serves them then).
+#define VAR_GATE(ctx, what)                                        \
+    do {                                                           \
+        if ((ctx) && (ctx)->var && !(ctx)->var_full) VAR_NOTIMPL(ctx, what); \
+    } while (0)
+static int var_set_full(pcl_ctx *ctx, int64_t on);
+static int var_set_goal(pcl_ctx *ctx, const double *goal_iso_vec);
+static int var_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns);
+static int var_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c);
+static int var_set_weights(pcl_ctx *ctx, const double *w);
+static int var_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad);
+static int var_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz);
+static int var_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols);
+static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals);
+static int var_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out);

@@ -66,6 +66,15 @@ struct pcl_ctx {
     int var_wG = 0, var_wD = 0, var_wV = 0;
     long long var_off_d = 0, var_voff_d = 0, var_off_v = 0, var_voff_v = 0;
     int64_t opt_var_blocks = 0, opt_var_cols = 0;  // ... block / column workgroups per interval of the fused launch (0 auto)
+    int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
+    std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
+    double *dvar_coef = nullptr; // ... the objective Hessian's coefficients [-s w_0 Q sigma | |x_i,N|^2]
+    // ... regularisers that cover a component with a dense triangle at the terminal knot (pcl_host_robust.hpp: var_hess_plan)
+    std::vector<int> var_last_src;    // kept slots of the terminal knot's regulariser block
+    std::vector<double> var_diag;     // [triangle][dt_power][x_dim of a component]: R summed over the covering regularisers
+    int *dvar_last_src = nullptr;
+    double *dvar_diag = nullptr, *dvar_scratch = nullptr;
+    long long var_scratch_cap = 0;
     long long x_dim;
     std::vector<int32_t> x_offs;
     int device;
@@ -641,7 +650,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
         for (auto &pr : t.ev)
             for (hipEvent_t e : pr)
                 if (e) (void)hipEventDestroy(e);
-    for (void *q : {(void *)ctx->dformA, (void *)ctx->dformc, (void *)ctx->dgram, (void *)ctx->dcoef})
+    for (void *q : {(void *)ctx->dformA, (void *)ctx->dformc, (void *)ctx->dgram, (void *)ctx->dcoef, (void *)ctx->dvar_coef, (void *)ctx->dvar_last_src, (void *)ctx->dvar_diag, (void *)ctx->dvar_scratch})
         if (q) (void)hipFree(q);
     for (void *q : {(void *)ctx->dsub, (void *)ctx->dweights, (void *)ctx->dregs, (void *)ctx->dreg_R, (void *)ctx->dobj, (void *)ctx->dphik, (void *)ctx->dmcols, (void *)ctx->dmticket,
                     (void *)ctx->dgrad, (void *)ctx->dval})
@@ -2260,7 +2269,8 @@ extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, dou
 extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
-    VAR_NOTIMPL(ctx, "pcl_rollout_dev");
+    VAR_GATE(ctx, "pcl_rollout_dev");
+    if (ctx->var) return var_rollout_dev(ctx, Z, X_out);
     ON_DEVICE(ctx);
     KParams p;
     fill_params(ctx, p);
@@ -2434,7 +2444,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
 extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout: NULL pointer");
-    VAR_NOTIMPL(ctx, "pcl_rollout");
+    VAR_GATE(ctx, "pcl_rollout");
     ON_DEVICE(ctx);
     const long long nv = (long long)ctx->win_count * ctx->desc.N * ctx->x_dim;
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
@@ -2447,5 +2457,6 @@ extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
 }
 
 #include "pcl_host_objective.hpp"
+#include "pcl_host_robust.hpp"
 #include "pcl_host_comm.hpp"
 #include "pcl_host_options.hpp"

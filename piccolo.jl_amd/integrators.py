@@ -26,7 +26,7 @@ from .trajectory import STATE, TIMESTEP, NamedTrajectory
 __all__ = [
     "HipPadeIntegrator", "HipPadeMemberIntegrator", "HipPadeMultistart", "DerivativeIntegrator", "BilinearIntegrator", "evaluate_", "eval_jacobian",
     "jacobian_structure", "hessian_structure", "eval_hessian_of_lagrangian", "PclError", "HipVariationalIntegrator", "VariationalUnitaryIntegrator",
-    "VariationalKetIntegrator",
+    "VariationalKetIntegrator", "variational_rollout",
 ]  # fmt: skip
 
 
@@ -95,6 +95,9 @@ class _PclContext:
             self.compact_nnz, self.compact_per = a.value, b.value
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
         self.window = (0, batch)
+        # a variational context: x_dim is the stacked state; goals and forms speak of component 0, the rollout returns one stacked trajectory
+        self.variational = batch_mode == PCL_BATCH_VARIATIONAL
+        self.goal_dim = self.x_dim // batch if self.variational else self.x_dim
 
     def _chk(self, rc):
         if rc != 0:
@@ -266,8 +269,8 @@ class _PclContext:
     # -- terminal infidelity objective on device ----------------------------------------------------------------
     def set_goal(self, goal_iso_vec):
         g = np.ascontiguousarray(goal_iso_vec, dtype=np.float64).reshape(-1)
-        if g.size != self.x_dim:
-            raise ValueError("goal iso-vec has %d entries, expected %d" % (g.size, self.x_dim))
+        if g.size != self.goal_dim:
+            raise ValueError("goal iso-vec has %d entries, expected %d" % (g.size, self.goal_dim))
         self._chk(self._L.pcl_set_goal(self._h, _ptr(g)))
 
     def set_goal_subspace(self, goal_sub_iso_vec, subspace):
@@ -280,7 +283,7 @@ class _PclContext:
 
     def set_goal_form(self, scope, A, c):
         """Terminal loss ``Q w |1 - F(x)|``, ``F = c'x + sum_r (A_r'x)^2`` (``pcl_set_goal_form``): scope 0 per member, 1 joint."""
-        L = self.x_dim * (self.batch if scope else 1)
+        L = self.goal_dim * (self.batch if scope and not self.variational else 1)
         A = None if A is None else np.ascontiguousarray(A, dtype=np.float64).reshape(-1, L)
         c = None if c is None else np.ascontiguousarray(c, dtype=np.float64).reshape(L)
         self._L.pcl_set_goal_form.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
@@ -360,7 +363,7 @@ class _PclContext:
     def rollout(self, Z, out=None):
         """[batch, N, x_dim] iso-vec states: X_{k+1} = exp(dt_k G(u_k)) X_k."""
         Z = self._z(Z)
-        out = np.empty((self.window[1], self.N, self.x_dim)) if out is None else out
+        out = np.empty((1 if self.variational else self.window[1], self.N, self.x_dim)) if out is None else out
         self._chk(self._L.pcl_rollout(self._h, _ptr(Z), _ptr(out)))
         return out
 
@@ -584,6 +587,33 @@ class HipVariationalIntegrator:
 
     def close(self):
         self._ctx.close()
+
+    def enable_objective_and_rollout(self):
+        """Switch the context's ``var_full`` option on: the objective entry points and the rollout then serve it (a freshly built integrator
+        refuses them).  ``Objective.bind``, ``rollout`` and ``variational_rollout`` call this themselves."""
+        if not self._ctx.get_option("var_full"):
+            self._ctx.set_option("var_full", 1)
+
+    def rollout(self, traj_or_Z):
+        """``[N, x_dim]``: the stacked states ``vcat(x, x_var_1, ..)`` at every knot by exact propagation under the lifted generator
+        (``x <- E x``, ``x_var_i <- E x_var_i + L_i x``), from the knot-0 state."""
+        self.enable_objective_and_rollout()
+        Z = traj_or_Z.datavec if hasattr(traj_or_Z, "datavec") else traj_or_Z
+        return self._ctx.rollout(Z)[0]
+
+    def rollout_dev(self, Z_dev, out_dev):
+        """Device buffers: ``Z_dev`` the variable vector, ``out_dev`` ``N * x_dim`` doubles."""
+        self.enable_objective_and_rollout()
+        self._ctx.rollout_dev(Z_dev, out_dev)
+
+
+def variational_rollout(B, traj):
+    """The stacked iso-vec states ``vcat(x, x_var_1, ..)`` at every knot, ``x_dim x N`` (next to ``unitary_rollout``): exact propagation of the
+    state and its sensitivities on the GPU.  ``B``: a ``VariationalUnitaryIntegrator`` / ``VariationalKetIntegrator``."""
+    if not isinstance(B, HipVariationalIntegrator):
+        raise TypeError("variational_rollout takes a variational integrator, got %s" % type(B).__name__)
+    B._check(traj)
+    return B.rollout(traj).T.copy()
 
 
 def _variational_generators(sys, scales):

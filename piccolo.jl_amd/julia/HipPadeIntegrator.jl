@@ -294,6 +294,73 @@ VariationalUnitaryIntegrator(sys, traj::NamedTrajectory, Ũ⃗::Symbol, Ũ⃗_va
                              scales::AbstractVector{<:Float64} = fill(1.0, length(sys.G_vars)), kwargs...) =
     _variational(sys, traj, Ũ⃗, Ũ⃗_variations, u, Vector{Float64}(scales), 0; kwargs...)
 
+# ---- robust control on a variational integrator: the objective and the rollout (context option "var_full") ----------------------------------
+_is_variational(B::HipPadeIntegrator) = length(getfield(B, :x_names)) > 1 && _core(B).n_members == 1
+function _enable_var_full!(B::HipPadeIntegrator)
+    _is_variational(B) || error("a variational integrator (VariationalUnitaryIntegrator / VariationalKetIntegrator) is required")
+    c = _core(B).ctx
+    check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_full", 1))
+    return c
+end
+
+# variational_rollout(B, traj): the stacked states vcat(x, x_var_1, ..) at every knot, x_dim x N, by exact propagation under the lifted
+# generator (x <- E x, x_var_i <- E x_var_i + L_i x) from the knot-0 state -- next to unitary_rollout [REF src/quantum/dynamics.jl:631-667]
+function variational_rollout(B::HipPadeIntegrator, traj::NamedTrajectory)
+    c = _enable_var_full!(B)
+    z = Vector{Float64}(vec(traj.datavec))
+    X = Matrix{Float64}(undef, getfield(B, :x_dim), traj.N)
+    check(c, ccall((:pcl_rollout, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), c, z, X))
+    return X
+end
+
+# bind_robust_objective!(B; goal_iso_vec, Q, sensitivities, regularizers): the objective of a robust-control problem on the device,
+#     Q |1 - F(U_N)| + sum_i Qs_i scale_i^4 |tr(U_var_i' U_var_i)|^2 / n^2 (terminal knot) + regularisers
+# [REF UnitaryInfidelityObjective objectives.jl:347-356; UnitarySensitivityObjective objectives.jl:437-453, used at [traj.N] by
+# src/specs/materialize.jl:306-307].  sensitivities: variation name => (Qs, scale); times other than [traj.N] are not implemented.
+# regularizers: (name, R::Vector{Float64}, dt_power).  Returns (value_and_gradient, hessian_structure, hessian) closures over the context.
+function bind_robust_objective!(B::HipPadeIntegrator, traj::NamedTrajectory; goal_iso_vec::Union{Nothing,Vector{Float64}} = nothing, Q::Float64 = 100.0,
+                                sensitivities::AbstractDict{Symbol,<:Tuple{Real,Real}} = Dict{Symbol,Tuple{Float64,Float64}}(),
+                                times::AbstractVector{<:Integer} = [traj.N], regularizers = ())
+    times == [traj.N] || error("sensitivity terms at the terminal knot only: times must be [$(traj.N)], got $times")
+    names = getfield(B, :x_names)
+    c = _enable_var_full!(B)
+    w = zeros(length(names)); w[1] = 1.0
+    for (nm, (Qs, scale)) in sensitivities
+        i = findfirst(==(nm), names)
+        (i === nothing || i == 1) && error("the sensitivity term names $nm; it must name one of the variations $(names[2:end])")
+        w[i] += Qs * scale^4
+    end
+    check(c, ccall((:pcl_clear_regularizers, LIB), Cint, (Ptr{Cvoid},), c))
+    for (nm, R, p) in regularizers
+        r = traj.components[nm]
+        Rv = Vector{Float64}(R)
+        check(c, ccall((:pcl_add_regularizer, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int32), c, r[1] - 1, length(r), Rv, p))
+    end
+    goal_iso_vec === nothing || check(c, ccall((:pcl_set_goal, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), c, goal_iso_vec))
+    check(c, ccall((:pcl_set_weights, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), c, w))
+    nv = getfield(B, :n_vars)
+    function value_and_gradient(z::Vector{Float64})
+        val = Ref{Float64}(0.0); g = Vector{Float64}(undef, nv)
+        check(c, ccall((:pcl_objective, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Ref{Float64}, Ptr{Float64}), c, z, Q, val, g))
+        return val[], g
+    end
+    function hessian_structure()   # queried AFTER the weights and regularisers are set: it depends on them
+        n = Ref{Int64}(0)
+        check(c, ccall((:pcl_objective_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), c, n))
+        rows = Vector{Int64}(undef, n[]); cols = similar(rows)
+        check(c, ccall((:pcl_objective_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), c, rows, cols))
+        return rows, cols
+    end
+    function hessian(z::Vector{Float64}, σ::Float64 = 1.0)
+        n = Ref{Int64}(0)
+        check(c, ccall((:pcl_objective_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), c, n))
+        vals = Vector{Float64}(undef, n[])
+        check(c, ccall((:pcl_objective_hess, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64, Float64, Ptr{Float64}), c, z, Q, σ, vals))
+        return vals
+    end
+    return value_and_gradient, hessian_structure, hessian
+end
+
 function _fresh!(core::PclCore, z::AbstractVector{Float64})
     if length(core.z) != length(z) || core.z != z
         core.z = copy(z)
@@ -462,5 +529,5 @@ function Base.getproperty(B::HipPadeIntegrator, s::Symbol)
 end
 Base.propertynames(B::HipPadeIntegrator, private::Bool = false) = (fieldnames(HipPadeIntegrator)..., :f, :ctx)
 
-export HipPadeIntegrator, VariationalKetIntegrator, VariationalUnitaryIntegrator
+export HipPadeIntegrator, VariationalKetIntegrator, VariationalUnitaryIntegrator, variational_rollout, bind_robust_objective!
 end # module

@@ -5,6 +5,7 @@ the C ABI (``pcl_set_goal[_subspace]``, ``pcl_set_weights``, ``pcl_add_regulariz
   ... with an EmbeddedOperator goal (subspace fidelity)     src/control/objectives.jl:339-345
   QuadraticRegularizer(name, traj, R) [EXT DirectTrajOpt]   src/control/templates/smooth_pulse_problem.jl:249-251
   sum_i (w_i Q) l_i + regularisers (SamplingProblem)        src/control/templates/sampling_problem.jl:381-387
+  UnitarySensitivityObjective(name, traj, [N]; Qs, scale)   src/control/objectives.jl:437-453   (robust control, variational integrators)
 
 Terms are small records combined with ``+`` (as the reference combines ``AbstractObjective``s); ``bind`` attaches the sum
 to an integrator's context, after which ``value_and_gradient(traj)`` is one call into the library.  Nothing here computes
@@ -15,7 +16,7 @@ import numpy as np
 from .quantum import compact_iso_to_density, operator_to_iso_vec
 
 __all__ = ["EmbeddedOperator", "UnitaryInfidelityObjective", "QuadraticRegularizer", "Objective", "get_subspace_indices",
-           "KetInfidelityObjective", "CoherentKetInfidelityObjective", "DensityMatrixInfidelityObjective", "DensityMatrixPureStateInfidelityObjective"]  # fmt: skip
+           "UnitarySensitivityObjective", "KetInfidelityObjective", "CoherentKetInfidelityObjective", "DensityMatrixInfidelityObjective", "DensityMatrixPureStateInfidelityObjective"]  # fmt: skip
 
 
 def get_subspace_indices(subspaces, subsystem_levels):
@@ -65,6 +66,31 @@ class UnitaryInfidelityObjective(_Term):
         self.goal, self.Q = U_goal, float(Q)
         self.names = [names] if isinstance(names, str) else list(names)
         self.weights = None if weights is None else np.asarray(weights, dtype=np.float64)
+
+
+class UnitarySensitivityObjective(_Term):
+    """``Qs[0] * scale^4 * |tr(U_var' U_var)|^2 / n^2`` on the variation component ``name`` at the terminal knot
+    [REF src/control/objectives.jl:437-453, used at ``[traj.N]`` by src/specs/materialize.jl:306-307]; ``times`` are the reference's 1-based
+    knot indices.  Only the terminal knot is implemented: any other entry raises ``NotImplementedError``.  Bound to a
+    ``VariationalUnitaryIntegrator`` next to the infidelity of the state itself."""
+
+    def __init__(self, name, traj, times, Qs=None, scale=1.0):
+        times = [int(t) for t in np.atleast_1d(times)]
+        if name not in traj.components:
+            raise KeyError("trajectory has no component %r" % (name,))
+        if times != [traj.N]:
+            raise NotImplementedError("sensitivity terms at the terminal knot only: times must be [%d], got %r" % (traj.N, times))
+        Qs = np.ones(len(times)) if Qs is None else np.asarray(Qs, dtype=np.float64).reshape(-1)
+        if Qs.size != len(times):
+            raise ValueError("expected %d weights Qs, got %d" % (len(times), Qs.size))
+        if not np.isfinite(Qs).all() or (Qs < 0).any() or not np.isfinite(scale):
+            raise ValueError("Qs must be finite and >= 0, scale finite")
+        self.name, self.times, self.Qs, self.scale = name, times, Qs, float(scale)
+
+    @property
+    def weight(self):
+        """The coefficient of ``(|x|^2)^2 / d^2`` the device term takes."""
+        return float(self.Qs[0]) * self.scale**4
 
 
 def _ket_rows(goal):
@@ -179,6 +205,11 @@ class Objective:
         inf = [t for t in self.terms if isinstance(t, (UnitaryInfidelityObjective, _FormTerm))]
         if len(inf) > 1:
             raise NotImplementedError("one terminal infidelity term per problem")
+        sens = [t for t in self.terms if isinstance(t, UnitarySensitivityObjective)]
+        if len(members) == 1 and getattr(members[0].ctx, "variational", False):
+            return self._bind_variational(members[0], inf, sens)
+        if sens:
+            raise ValueError("a UnitarySensitivityObjective needs a variational integrator (VariationalUnitaryIntegrator)")
         cores = {id(b.ensemble) for b in members if hasattr(b, "ensemble")}
         shared = len(cores) == 1 and all(hasattr(b, "ensemble") for b in members)
         if len(members) > 1 and not shared and any(hasattr(b, "ensemble") for b in members):
@@ -231,6 +262,49 @@ class Objective:
             if inf or i == 0:  # (a context that carries no term -- regularisers live on the first one -- is not evaluated)
                 self._bound.append((ctx, w_host))
         self._ctx = ctxs[0]
+        return self
+
+    def _bind_variational(self, B, inf, sens):
+        """One variational context: the infidelity names the state (component 0), every sensitivity term a variation; ``Qs[0] * scale^4``
+        becomes that variation's weight."""
+        names = list(B.x_names)
+        w = np.zeros(len(names))
+        w[0] = 1.0
+        if inf:
+            t = inf[0]
+            if list(t.names) != names[:1]:
+                raise ValueError("the infidelity term names %r; on a variational integrator it must name the state %r (component 0)" % (list(t.names), names[0]))
+            if t.weights is not None:
+                if t.weights.size != 1:
+                    raise ValueError("expected 1 weight, got %d" % t.weights.size)
+                w[0] = float(t.weights[0])
+        for t in sens:
+            if t.name not in names[1:]:
+                raise ValueError("the sensitivity term names %r; it must name one of the variations %r" % (t.name, names[1:]))
+            w[names.index(t.name)] += t.weight
+        B.enable_objective_and_rollout()
+        ctx = B.ctx
+        ctx.clear_regularizers()
+        for t in self.terms:
+            if isinstance(t, QuadraticRegularizer):
+                ctx.add_regularizer(t.off, t.dim, t.R, t.dt_power)
+        self._Q = 0.0
+        if inf and isinstance(inf[0], _FormTerm):
+            scope, A, c = inf[0].form(ctx.goal_dim, 1)
+            if scope != 0:
+                raise NotImplementedError("a joint terminal loss on a variational integrator")
+            ctx.set_goal_form(0, A, c)
+            self._Q = inf[0].Q
+        elif inf:
+            t = inf[0]
+            if isinstance(t.goal, EmbeddedOperator):
+                ctx.set_goal_subspace(operator_to_iso_vec(t.goal.unembed()), t.goal.subspace)
+            else:
+                ctx.set_goal(operator_to_iso_vec(np.asarray(t.goal, dtype=complex)))
+            self._Q = t.Q
+        ctx.set_weights(w)
+        self._bound = [(ctx, 1.0)]
+        self._ctx = ctx
         return self
 
     def value_and_gradient(self, traj_or_Z, want_grad=True):
