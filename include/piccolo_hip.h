@@ -83,6 +83,25 @@ typedef enum pcl_status {
                           outputs of that launch are incomplete; returned by the next evaluator entry point or pcl_sync, then cleared */
 } pcl_status;
 
+/* pcl_desc.pade_order: the EXACT exponential constraint instead of a diagonal Pade discretisation of it,
+ *     delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k
+ * -- the reference's own (docs/src/concepts/index.md:21) -- for steps too large for order 10 (the order policy's order_tol_met = 0).  Chosen at
+ * creation only; nothing switches to it on its own.  Shapes: unitary, ket, PCL_STATE_VECTOR; PCL_BATCH_MEMBERS (shared or per-member G0) and
+ * PCL_BATCH_TRAJ with the member window; m = 0; PCL_BATCH_VARIATIONAL: PCL_ENOTIMPL.  Rows as always.  Jacobian values per (member b, interval k),
+ * jac_nnz_per_interval = cols*n*n + x_dim*(m + 2) doubles (reported by pcl_jac_structure, never assumed), E = exp(h G), L_l the Frechet derivative
+ * of exp at h G along h G_l:
+ *     seg 0  d delta/d X_k      for c<cols, j<n, i<n : -E[i,j]   row c*n+i, col x_off + c*n+j     (knot k)
+ *     seg 1  d delta/d X_{k+1}  for r<x_dim          : +1        row r,     col x_off + r         (knot k+1; the identity as its diagonal)
+ *     tail   per state column c: for l<m, i<n : -(L_l X_k)[i,c]  col u_off + l ; then i<n : -(G E X_k)[i,c]  col dt_off   (the Pade layout)
+ * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
+ * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, pcl_rollout[_dev] and the whole
+ * objective family -- the last three with the bits a Pade context of the same system gives.  PCL_ENOTIMPL: pcl_hess[_dev], pcl_hess_nnz,
+ * pcl_hess_structure[_i64] (the (u_i, u_j) block of the Hessian of the Lagrangian needs second Frechet derivatives; solve with a quasi-Newton
+ * Hessian, the reference's eval_hessian = false), the compact Jacobian trio and the merit / reduce entry points.  pcl_set_order_policy and
+ * pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  get_option "pade_order" reads -1, "last_kernel" 100 (residual +
+ * Jacobian) or 101 (residual only). */
+#define PCL_ORDER_EXP (-1)
+
 #define PCL_MAX_D 32 /* n = 2d <= 64: G(u_k), G^2 and the column tiles stay LDS-resident */
 
 /* batch_mode */
@@ -127,7 +146,8 @@ typedef struct pcl_desc {
     int32_t batch;       /* number of members / seeds (>= 1) */
     int32_t batch_mode;  /* PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ or PCL_BATCH_VARIATIONAL */
     int32_t pade_order;  /* diagonal Pade order p of B^{+-}_p: 2, 4, 6, 8 or 10; 0: the smallest order whose deviation from the reference's
-                            exp constraint is below a tolerance -- pcl_set_order_policy, or the first host-pointer call decides */
+                            exp constraint is below a tolerance -- pcl_set_order_policy, or the first host-pointer call decides;
+                            PCL_ORDER_EXP: the exponential constraint itself (see there) */
     int32_t device_id;   /* HIP device ordinal */
     int32_t index_base;  /* 0 (C/Python) or 1 (Julia/MOI) for the emitted structure */
     int32_t per_member_G0; /* 0: one G0 for all members; 1: G0 holds batch matrices (per-member H_drift) */

@@ -358,6 +358,7 @@ extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *va
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
     VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
+    EXP_NOTIMPL(ctx, "pcl_merit_grad_dev");
     if (!ctx) return PCL_EINVAL;
     if (!delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_merit_grad_dev: NULL pointer");
     ON_DEVICE(ctx);
@@ -378,6 +379,7 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
+    EXP_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");
     ctx->merit_want = 1;
@@ -599,6 +601,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
+    EXP_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out || !value) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: no goal set");
@@ -628,6 +631,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
     VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
+    EXP_NOTIMPL(ctx, "pcl_merit_grad_len");
     if (!ctx) return PCL_EINVAL;
     if (len) *len = 1 + (int64_t)ctx->K * ctx->desc.n_drives + ctx->K;
     if (sets) *sets = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;

@@ -8,6 +8,7 @@
 //   pcl_kernels_hessian.hpp    Hessian of the Lagrangian: versions 1 (one workgroup per interval) and 2 (column chunks, fallback)
 //   pcl_kernel_hessian_v3.hpp  Hessian of the Lagrangian, default: one workgroup per interval, jobs split by drive
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
+//   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -45,6 +46,7 @@
 #include "pcl_kernel_hessian_v3.hpp"
 #include "pcl_kernels_misc.hpp"
 #include "pcl_kernels_objective.hpp"
+#include "pcl_kernel_exp.hpp"
 #include "pcl_host_expand.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -57,6 +59,7 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
+    int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order, no Hessian, no compact Jacobian
     int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
     long long var_xdc = 0;  // ... x_dim of one component
     int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
@@ -312,6 +315,7 @@ static int v4_power_tiles(int d, int m, int q, size_t max_lds) {
 static long long var_jac_per(const pcl_ctx *c);
 static long long jac_per_full(const pcl_ctx *c) {
     if (c->var) return var_jac_per(c);
+    if (c->exp) return (long long)c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 2);  // -E copies | the diagonal of I | tails
     return 2LL * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
 static long long jac_per_compact(const pcl_ctx *c) { return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1); }
@@ -339,6 +343,13 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 
 #include "pcl_host_variational.hpp"
 
+// The exponential mode (PCL_ORDER_EXP) serves the residual, the Jacobian, the rollout and the objective family.  The Hessian of the Lagrangian (its
+// (u_i, u_j) block needs second Frechet derivatives: DESIGN.md section 8), the compact Jacobian and the merit / reduce payload are refused in these words.
+#define EXP_NOTIMPL(ctx, what)                                                                                                                      \
+    do {                                                                                                                                            \
+        if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
+    } while (0)
+
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (!out) return fail(nullptr, PCL_EINVAL, "pcl_create: out is NULL");
     *out = nullptr;
@@ -346,6 +357,8 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
+    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL && dsc->pade_order == PCL_ORDER_EXP)
+        return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented");
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL) return var_create(dsc, out);
     const bool vec = dsc->state_cols == PCL_STATE_VECTOR;  // general real d x d generator on one real column
     const int d = dsc->d, m = dsc->n_drives, n = vec ? d : 2 * d;
@@ -355,7 +368,9 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (n > 2 * PCL_MAX_D)
         return fail(nullptr, PCL_ESHAPE, "pcl_create: generator dimension %d exceeds %d (LDS-resident tiles; d <= %d)", n, 2 * PCL_MAX_D, PCL_MAX_D);
     if (m > 24) return fail(nullptr, PCL_ESHAPE, "pcl_create: n_drives=%d exceeds 24", m);
-    if (dsc->pade_order != 0 && dsc->pade_order != 2 && dsc->pade_order != 4 && dsc->pade_order != 6 && dsc->pade_order != 8 && dsc->pade_order != 10)
+    if (dsc->pade_order < PCL_ORDER_EXP)
+        return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order=%d; accepted values are the diagonal Pade orders 2, 4, 6, 8, 10, 0 (chosen by pcl_set_order_policy) and PCL_ORDER_EXP (-1, the exponential constraint)", dsc->pade_order);
+    if (dsc->pade_order != PCL_ORDER_EXP && dsc->pade_order != 0 && dsc->pade_order != 2 && dsc->pade_order != 4 && dsc->pade_order != 6 && dsc->pade_order != 8 && dsc->pade_order != 10)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order=%d; diagonal Pade orders 2, 4, 6, 8, 10 are implemented (0: chosen by pcl_set_order_policy)", dsc->pade_order);
     if (dsc->index_base != 0 && dsc->index_base != 1) return fail(nullptr, PCL_EINVAL, "pcl_create: index_base must be 0 or 1");
     if (dsc->batch_mode != PCL_BATCH_MEMBERS && dsc->batch_mode != PCL_BATCH_TRAJ)
@@ -387,6 +402,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     ctx->x_dim = x_dim;
     ctx->cols = cols;
     ctx->vec = vec ? 1 : 0;
+    ctx->exp = dsc->pade_order == PCL_ORDER_EXP ? 1 : 0;
     ctx->x_offs.assign(dsc->x_offs, dsc->x_offs + n_off);
     ctx->hG0.assign(dsc->G0, dsc->G0 + (size_t)n * n * (dsc->per_member_G0 ? dsc->batch : 1));
     if (m > 0) ctx->hGj.assign(dsc->Gj, dsc->Gj + (size_t)m * n * n);
@@ -549,7 +565,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
         for (int l = 0; l < m; ++l) iso = iso && is_iso(dsc->Gj + l * nn);
     ctx->iso = iso ? 1 : 0;
     // pattern-compiled kernels: sparse iso generators of a unitary problem, one state column per lane (d <= 32), m + 2 waves
-    if (iso && cols == d && d >= 9 && d <= 32 && m >= 1 && m <= 6) {
+    if (iso && cols == d && d >= 9 && d <= 32 && m >= 1 && m <= 6 && !ctx->exp) {  // (the exponential mode has its one kernel)
         pcl_codegen::SpPlan plan = pcl_codegen::make_plan(d, m, dsc->G0, dsc->per_member_G0 ? dsc->batch : 1, dsc->Gj);
         if (plan.ok && plan.nz <= 640 && (double)plan.nz <= 0.45 * 2.0 * d * d) ctx->sp_plan = new pcl_codegen::SpPlan(std::move(plan));
     }
@@ -559,7 +575,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     }
     std::vector<double> g0(dsc->G0, dsc->G0 + nn * (dsc->per_member_G0 ? dsc->batch : 1));
     CREATE_TRY(upload(ctx, &ctx->dG0, g0));
-    if (n <= 16 && m >= 1) {
+    if ((n <= 16 || ctx->exp) && m >= 1) {  // (... and the exponential mode at every n: the directions of its Frechet pairs)
         std::vector<double> gjd(dsc->Gj, dsc->Gj + nn * m);
         CREATE_TRY(upload(ctx, &ctx->dGjd, gjd));
     }
@@ -699,12 +715,14 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
     VAR_NOTIMPL(ctx, "pcl_jac_compact_nnz");
+    EXP_NOTIMPL(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
     if (nnz) *nnz = jac_per_compact(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
+    EXP_NOTIMPL(ctx, "pcl_hess_nnz");
     if (per) *per = hess_per(ctx);
     if (nnz) *nnz = hess_per(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
@@ -726,7 +744,20 @@ static int jac_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
             I *r = rows + (b * ctx->K + k) * per, *c = cols + (b * ctx->K + k) * per;
             const long long r0 = b * xd * ctx->K + k * xd + base;
             long long p = 0;
-            for (int seg = 0; seg < 2; ++seg) {
+            if (ctx->exp) {  // d/dX_{k+1} = I: its diagonal, after the copies of -E
+                const long long cb = voff + k * zd + xo + base, cn = voff + (k + 1) * zd + xo + base;
+                for (long long cc = 0; cc < d; ++cc)
+                    for (long long j = 0; j < n; ++j)
+                        for (long long i = 0; i < n; ++i, ++p) {
+                            r[p] = (I)(r0 + cc * n + i);
+                            c[p] = (I)(cb + cc * n + j);
+                        }
+                for (long long q = 0; q < xd; ++q, ++p) {
+                    r[p] = (I)(r0 + q);
+                    c[p] = (I)(cn + q);
+                }
+            }
+            for (int seg = 0; seg < 2 && !ctx->exp; ++seg) {
                 const long long cb = voff + (k + seg) * zd + xo + base;
                 for (long long cc = 0; cc < d; ++cc)
                     for (long long j = 0; j < n; ++j)
@@ -760,6 +791,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
+    EXP_NOTIMPL(ctx, "pcl_hess_structure");
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
     const long long m = D.n_drives, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
@@ -1342,6 +1374,29 @@ static int launch_pade_general(pcl_ctx *ctx, KParams &p, bool want_jac) {
     return PCL_OK;
 }
 
+// The exponential mode: one workgroup per (member, interval, drive) for residual + Jacobian, per (member, interval) for the residual alone
+// (pcl_kernel_exp.hpp).  G_l has an LDS tile of its own where the five tiles and the X_k tile fit.
+static int launch_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
+    const size_t tile = (size_t)p.LD * p.n;
+    const bool fre = want_jac && p.m > 0;
+    size_t dbl = (want_jac ? 4 : 3) * tile + (size_t)p.LD * p.cols + 32 + 64;
+    int gl_lds = 0;
+    if (fre && (dbl + tile) * sizeof(double) <= (size_t)ctx->max_lds) gl_lds = 1, dbl += tile;
+    const size_t lds = dbl * sizeof(double);
+    if (lds > (size_t)ctx->max_lds) return fail(ctx, PCL_ESHAPE, "the exponential kernel needs %zu B of LDS (> %d) for n=%d, %d columns", lds, ctx->max_lds, p.n, p.cols);
+    const long long grid = (long long)p.batch * p.K * (want_jac ? std::max(p.m, 1) : 1);
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    typedef void (*kexp_t)(const KParams, const double *, int);
+    const kexp_t kern = want_jac ? (kexp_t)pcl_exp_kernel<true> : (kexp_t)pcl_exp_kernel<false>;
+    if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 0 : 2, lds)) return rc;
+    const unsigned threads = p.n > 32 ? 512 : 256;  // (more than eight 16 x 16 output tiles per product: eight waves, a pair of tiles each)
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, p, (const double *)ctx->dGjd, gl_lds);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_kernel = want_jac ? 100 : 101;  // the exponential kernel: fused | residual only
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
 static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where);
 static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *jac, bool compact) {
     ON_DEVICE(ctx);
@@ -1351,6 +1406,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
         return var_launch_fused(ctx, Z, delta, jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
+    if (ctx->exp && compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
     KParams p;
     fill_params(ctx, p);
     p.Z = Z + (ctx->desc.batch_mode == PCL_BATCH_TRAJ ? (long long)ctx->win_first * ctx->desc.z_dim * ctx->desc.N : 0);
@@ -1359,6 +1415,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
+    if (ctx->exp) return launch_exp(ctx, p, want_jac);
     // streaming stores of the Jacobian blocks (auto): write-through while the launch's values fit the infinity cache with room to
     // spare (one trajectory of config 3: 133 MB), plain write-back above (see store2)
     if (ctx->opt_nt < 0 && want_jac && !compact && (long long)ctx->win_count * ctx->K * jac_per_full(ctx) * 8 <= (192LL << 20)) p.nt = 2;
@@ -1626,6 +1683,7 @@ static size_t hess2_lds_bytes(const KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
+    EXP_NOTIMPL(ctx, "pcl_hess");
     if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);
     if (int rc = resolve_order(ctx, nullptr, "pcl_hess")) return rc;
     KParams p;
@@ -2060,8 +2118,8 @@ static int order_for(double theta, double tol, bool *met = nullptr) {
 static void note_order(pcl_ctx *ctx, double theta, bool met) {
     ctx->order_tol_met = met ? 1 : 0;
     if (!met) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "order policy: |dt G| <= %.3g is too large for any diagonal Pade order up to 10 to stay within %.3g of the exp constraint; order 10 is used (option order_tol_met = 0)", theta, ctx->order_tol);
+        char buf[320];
+        snprintf(buf, sizeof buf, "order policy: |dt G| <= %.3g is too large for any diagonal Pade order up to 10 to stay within %.3g of the exp constraint; order 10 is used (option order_tol_met = 0), or create the context with PCL_ORDER_EXP", theta, ctx->order_tol);
         ctx->err = buf;
         if (getenv("PCL_VERBOSE")) fprintf(stderr, "piccolo_hip: %s\n", buf);
     }
@@ -2124,6 +2182,7 @@ extern "C" int pcl_order_for_bounds(int32_t n, int32_t m, const double *G0, int3
 }
 extern "C" int pcl_set_order_policy(pcl_ctx *ctx, double dt_max, const double *u_max, double tol, int32_t *order_out) {
     if (!ctx) return PCL_EINVAL;
+    if (ctx->exp) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: the context evaluates the exponential constraint; there is no order to choose");
     if (!(dt_max > 0.0) || !(tol > 0.0) || (ctx->desc.n_drives > 0 && !u_max)) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: need dt_max > 0, tol > 0 and the drives' bounds");
 #ifdef PCL_LAB
     if (ctx->res.active) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: a resident evaluator is running (pcl_resident_stop first)");
@@ -2169,6 +2228,7 @@ static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where) 
 
 extern "C" int pcl_set_order_from_trajectory(pcl_ctx *ctx, const double *Z_host, double tol, int32_t *order_out) {
     if (!ctx) return PCL_EINVAL;
+    if (ctx->exp) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: the context evaluates the exponential constraint; there is no order to choose");
     if (!Z_host) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: NULL trajectory");
 #ifdef PCL_LAB
     if (ctx->res.active) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: a resident evaluator is running (pcl_resident_stop first)");
@@ -2236,12 +2296,14 @@ extern "C" int pcl_jac_dev(pcl_ctx *ctx, const double *Z, double *vals) {  // ev
 extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *delta, double *compact) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !compact) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_compact_dev: NULL pointer");
+    EXP_NOTIMPL(ctx, "pcl_eval_jac_compact_dev");
     return launch_fused(ctx, Z, delta, compact, true);
 }
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
     VAR_NOTIMPL(ctx, "pcl_jac_expand_dev");
+    EXP_NOTIMPL(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
     const long long n_bk = (long long)ctx->win_count * ctx->K;
     if (ctx->cols == 1) {  // one state column (kets, compact density vectors): the compact layout IS the full layout
@@ -2343,7 +2405,7 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const auto t_begin = std::chrono::steady_clock::now();
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var;  // (variational contexts: full values, host_path 1)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var && !ctx->exp;  // (variational and exponential contexts: full values, host_path 1)
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -2427,6 +2489,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
+    EXP_NOTIMPL(ctx, "pcl_hess");
     ON_DEVICE(ctx);
     TRY(resolve_order(ctx, Z, "pcl_hess"));
     const long long nv = hess_per(ctx) * ctx->win_count * ctx->K;

@@ -58,6 +58,7 @@ class _PclContext:
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0):  # fmt: skip
         self._L = _lib.load()
         self._h = None
+        pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         n = d if state_cols == _lib.PCL_STATE_VECTOR else 2 * d  # PCL_STATE_VECTOR: general d x d generator, one column
         g0 = _colmajor(G0)
         gj = _colmajor(Gj) if m else np.zeros(1)
@@ -86,9 +87,14 @@ class _PclContext:
         self.x_dim, self.n_rows, self.n_cols = a.value, b.value, c.value
         self._chk(self._L.pcl_jac_nnz(h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz, self.jac_per = a.value, b.value
-        self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
-        self.hess_nnz, self.hess_per = a.value, b.value
-        if batch_mode == PCL_BATCH_VARIATIONAL:  # (no compact Jacobian for the stacked state)
+        # the exponential constraint: no Hessian of the Lagrangian and no compact Jacobian (hess_structure / hess raise with the library's message)
+        self.exponential = pade_order == _lib.PCL_ORDER_EXP
+        if self.exponential:
+            self.hess_nnz = self.hess_per = 0
+        else:
+            self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
+            self.hess_nnz, self.hess_per = a.value, b.value
+        if batch_mode == PCL_BATCH_VARIATIONAL or self.exponential:  # (no compact Jacobian for the stacked state)
             self.compact_nnz = self.compact_per = 0
         else:
             self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
@@ -128,7 +134,7 @@ class _PclContext:
 
     @property
     def pade_order(self):
-        """The order in use (0: a context created with ``pade_order=0`` that has not seen a policy or a trajectory yet)."""
+        """The order in use (0: a context created with ``pade_order=0`` that has not seen a policy or a trajectory yet; -1: the exponential constraint)."""
         return self.get_option("pade_order")
 
     def close(self):
@@ -238,6 +244,8 @@ class _PclContext:
         self.n_rows = b.value
         self._chk(self._L.pcl_jac_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz = a.value
+        if self.exponential:  # (no Hessian of the Lagrangian, no compact Jacobian)
+            return
         self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.hess_nnz = a.value
         self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
@@ -451,7 +459,9 @@ class HipPadeIntegrator:
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
         pointers, the scalar form ``f`` -- evaluates one order from the first call on.  ``pade_order=2..10`` pins the order
-        (BASELINE.json's metric is quoted on 4, which deviates from the exp constraint by 1.6e-5 at config 3)."""
+        (BASELINE.json's metric is quoted on 4, which deviates from the exp constraint by 1.6e-5 at config 3).  ``pade_order="exp"`` (or -1):
+        the exponential constraint itself, ``x_{k+1} - exp(dt_k G(u_k)) x_k`` -- for steps too large for order 10 (``order_tol_met`` False); residual
+        and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own."""
         x_names = [x_name] if isinstance(x_name, str) else list(x_name)
         G_drives = np.asarray(G_drives, dtype=np.float64)
         G_drift = np.asarray(G_drift, dtype=np.float64)

@@ -104,7 +104,8 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     M = length(x_offs)
     check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     jac_per = Int(nnz[]) ÷ M
-    check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    # (PCL_ORDER_EXP: no Hessian of the Lagrangian -- hess_per = 0, the structure is empty, pcl_hess is refused by the library)
+    pade_order == PCL_ORDER_EXP ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     return core, Int(ncol[])
@@ -119,7 +120,7 @@ function _member_structure(core::PclCore, member::Int)
     jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
     check(core.ctx, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), core.ctx, jr, jc))
     hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
-    check(core.ctx, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), core.ctx, hr, hc))
+    core.hess_per > 0 && check(core.ctx, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), core.ctx, hr, hc))
     _window!(core, 0, core.n_members)
     return jr, jc, hr, hc
 end
@@ -164,8 +165,15 @@ function _order_from_bounds!(core::PclCore, traj::NamedTrajectory, u_name::Symbo
     return Int(order[])
 end
 
+# pade_order = :exp (or PCL_ORDER_EXP = -1): the exponential constraint itself, x_{k+1} - exp(dt_k G(u_k)) x_k -- for steps too large for
+# order 10; residual and Jacobian only (solve with eval_hessian = false, the reference's default).  Never chosen on its own.
+const PCL_ORDER_EXP = -1
+_order_code(p::Integer) = Int(p)
+_order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
+
 function _integrators(G0s, Gj, traj::NamedTrajectory, names::Vector{Symbol}, u_name::Symbol;
-                      state_cols::Integer = 0, pade_order::Integer = 0, order_tol::Float64 = 1e-10, kwargs...)
+                      state_cols::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, kwargs...)
+    pade_order = _order_code(pade_order)
     x_offs = Int32[traj.components[nm][1] - 1 for nm in names]
     core, n_vars = _create_core(G0s, Gj, traj.N, traj.dim, traj.components[u_name][1] - 1,
                                 traj.components[traj.timestep][1] - 1, x_offs, traj.global_dim;
