@@ -96,10 +96,21 @@ typedef enum pcl_status {
  * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
  * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, pcl_rollout[_dev] and the whole
  * objective family -- the last three with the bits a Pade context of the same system gives.  PCL_ENOTIMPL: pcl_hess[_dev], pcl_hess_nnz,
- * pcl_hess_structure[_i64] (the (u_i, u_j) block of the Hessian of the Lagrangian needs second Frechet derivatives; solve with a quasi-Newton
- * Hessian, the reference's eval_hessian = false), the compact Jacobian trio and the merit / reduce entry points.  pcl_set_order_policy and
- * pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  get_option "pade_order" reads -1, "last_kernel" 100 (residual +
- * Jacobian) or 101 (residual only). */
+ * pcl_hess_structure[_i64] (the (u_i, u_j) block of the Hessian of the Lagrangian needs second Frechet derivatives: opt in below, or solve
+ * with a quasi-Newton Hessian, the reference's eval_hessian = false), the compact Jacobian trio and the merit / reduce entry points.
+ * pcl_set_order_policy and pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  get_option "pade_order" reads -1,
+ * "last_kernel" 100 (residual + Jacobian) or 101 (residual only).
+ *
+ * The Hessian of the Lagrangian, by option: pcl_set_option(ctx, "exp_hess", 1) on such a context (0, the default: the refusals above, in the
+ * same words; 1 on any other context: PCL_EINVAL; reading works everywhere) makes the five Hessian entry points serve it, for every shape and
+ * batch mode of the mode with a generator dimension n <= 62 (five n x n LDS tiles; beyond: PCL_ESHAPE with the byte counts, from the option).
+ * Nothing involves X_{k+1} (delta_k is X_{k+1} minus something), so per (member b, interval k) there are
+ * hess_nnz_per_interval = (m+1)(m+2)/2 + x_dim*(m+1) doubles (reported by pcl_hess_nnz, never assumed) -- the Pade layout without its last two
+ * groups, lower triangle (row >= col), with M = the interval's multipliers as an n x cols matrix, L2 the second Frechet derivative of exp:
+ *     seg 0  (u_i, u_j), j <= i : -<M, L2(hG; hG_i, hG_j) X_k>        seg 3  for l<m, r<x_dim : (u_l, X_k[r])   -(L_l' M)[r]
+ *     seg 1  (dt, u_j)          : -<M, (G_j E + G L_j) X_k>           seg 4  for r<x_dim      : (dt,  X_k[r])   -((G E)' M)[r]
+ *     seg 2  (dt, dt)           : -<M, G G E X_k>
+ * get_option "last_hess_kernel" reads 100 after such a launch.  The other refusals of the mode do not depend on the option. */
 #define PCL_ORDER_EXP (-1)
 
 #define PCL_MAX_D 32 /* n = 2d <= 64: G(u_k), G^2 and the column tiles stay LDS-resident */

@@ -134,6 +134,80 @@ __device__ __forceinline__ void mfma_gemm_lds(const double *__restrict__ A, int 
     }
 }
 
+// The same product with an accumulating output and a scaled left operand:  C[0:M,0:Nc] = (ACC ? C : 0) + alpha op(A) B.
+//   The split of the output tiles over the waves, the operand maps and the order of the k steps are those of mfma_gemm_lds: a lane owns the
+//   same entries of C in every call of one shape, so the terms of a sum of products into one tile need no barrier between them.  A may live
+//   in LDS or in global memory (read through L2).  Used by the exponential Hessian kernel (pcl_kernel_exp_hess.hpp); mfma_gemm_lds itself
+//   is untouched, so every other kernel keeps its bits.
+template <bool TRANS_A, bool ACC>
+__device__ __forceinline__ void mfma_gemm_lds_acc(const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb,
+                                                  double *__restrict__ C, int ldc, int M, int Nc, int Kd, double alpha, int wave,
+                                                  int nwaves, int lane) {
+    const int rt_n = (M + 15) >> 4, ct_n = (Nc + 15) >> 4, ks_n = (Kd + 3) >> 2;
+    const int nt = rt_n * ct_n;
+    const int li = lane & 15, lk = lane >> 4;
+    for (int t0 = wave * 2; t0 < nt; t0 += nwaves * 2) {
+        const int t1 = t0 + 1;
+        const bool has1 = t1 < nt;
+        const int rt0 = t0 % rt_n, ct0 = t0 / rt_n;
+        const int rt1 = has1 ? t1 % rt_n : rt0, ct1 = has1 ? t1 / rt_n : ct0;
+        const int row0 = rt0 * 16 + li, col0 = ct0 * 16 + li;
+        const int row1 = rt1 * 16 + li, col1 = ct1 * 16 + li;
+        const bool r0 = row0 < M, c0 = col0 < Nc, r1 = has1 && row1 < M, c1 = has1 && col1 < Nc;
+        double4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+        if (ACC) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr0 = rt0 * 16 + lk + 4 * r, rr1 = rt1 * 16 + lk + 4 * r;
+                if (c0 && rr0 < M) acc0[r] = C[rr0 + ldc * col0];
+                if (c1 && rr1 < M) acc1[r] = C[rr1 + ldc * col1];
+            }
+        }
+        // four k steps at a time: every operand of the four is loaded (from a clamped, always valid address: no divergent branch) before the
+        // first of their products is issued, so a wave waits for one round trip per four steps, not per step
+        for (int ks = 0; ks < ks_n; ks += 4) {
+            double a0[4], b0[4], a1[4], b1[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int k = (ks + u) * 4 + lk;
+                const bool kok = k < Kd;
+                const bool pa0 = r0 && kok, pb0 = c0 && kok, pa1 = r1 && kok, pb1 = c1 && kok;
+                const double va0 = A[pa0 ? (TRANS_A ? k + lda * row0 : row0 + lda * k) : 0], vb0 = B[pb0 ? k + ldb * col0 : 0];
+                const double va1 = A[pa1 ? (TRANS_A ? k + lda * row1 : row1 + lda * k) : 0], vb1 = B[pb1 ? k + ldb * col1 : 0];
+                a0[u] = pa0 ? alpha * va0 : 0.0;
+                b0[u] = pb0 ? vb0 : 0.0;
+                a1[u] = pa1 ? alpha * va1 : 0.0;
+                b1[u] = pb1 ? vb1 : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (ks + u < ks_n) {
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[u], b0[u], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[u], b1[u], acc1, 0, 0, 0);
+                }
+        }
+        if (c0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr = rt0 * 16 + lk + 4 * r;
+                if (rr < M) C[rr + ldc * col0] = acc0[r];
+            }
+        }
+        if (c1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int rr = rt1 * 16 + lk + 4 * r;
+                if (rr < M) C[rr + ldc * col1] = acc1[r];
+            }
+        }
+    }
+}
+template <bool TRANS_A, bool ACC>
+__device__ __forceinline__ void gemm_lds_acc(const double *A, int lda, const double *B, int ldb, double *C, int ldc, int M, int Nc, int Kd,
+                                             double alpha) {
+    mfma_gemm_lds_acc<TRANS_A, ACC>(A, lda, B, ldb, C, ldc, M, Nc, Kd, alpha, threadIdx.x >> 6, blockDim.x >> 6, threadIdx.x & 63);
+}
+
 // Plain VALU version of the same contract (selected with option use_mfma = 0; used to A/B the
 // matrix-core path and as a second implementation in the parity tests).
 template <bool TRANS_A>

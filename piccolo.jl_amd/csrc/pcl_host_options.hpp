@@ -22,6 +22,12 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     else if (!strcmp(key, "var_full")) {  // variational contexts: serve the objective and the rollout (0: refuse them, and drop goal, weights, regularisers)
         TRY(var_set_full(ctx, v));
     }
+    else if (!strcmp(key, "exp_hess")) {  // exponential contexts: serve the Hessian of the Lagrangian (0: refuse it, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "exp_hess must be 0 or 1");
+        if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_hess = 1 needs a context of the exponential constraint (PCL_ORDER_EXP)");
+        if (v) TRY(exp_hess_fits(ctx, "exp_hess = 1"));
+        ctx->exp_hess = (int)v;
+    }
 #ifdef PCL_PROFILE
     else if (!strcmp(key, "profile_flags"))  // profiling experiments (results may be WRONG); not present in the shipped library
         ctx->opt_prof = v;
@@ -157,6 +163,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->var;
     else if (!strcmp(key, "var_full"))
         *v = ctx->var_full;
+    else if (!strcmp(key, "exp_hess"))
+        *v = ctx->exp_hess;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

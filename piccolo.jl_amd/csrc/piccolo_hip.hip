@@ -9,6 +9,7 @@
 //   pcl_kernel_hessian_v3.hpp  Hessian of the Lagrangian, default: one workgroup per interval, jobs split by drive
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
 //   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
+//   pcl_kernel_exp_hess.hpp    ... its Hessian of the Lagrangian (option exp_hess): second Frechet derivatives, one chain per drive
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,7 @@
 #include "pcl_kernels_misc.hpp"
 #include "pcl_kernels_objective.hpp"
 #include "pcl_kernel_exp.hpp"
+#include "pcl_kernel_exp_hess.hpp"
 #include "pcl_host_expand.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -59,7 +61,10 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
-    int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order, no Hessian, no compact Jacobian
+    int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order, no compact Jacobian, the Hessian by option
+    int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
+    double *dexph = nullptr;     // ... its workspace: [G(u_k) | W_k | norm] per (member, interval)
+    long long exph_cap = 0;
     int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
     long long var_xdc = 0;  // ... x_dim of one component
     int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
@@ -321,6 +326,7 @@ static long long jac_per_full(const pcl_ctx *c) {
 static long long jac_per_compact(const pcl_ctx *c) { return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1); }
 static long long hess_per(const pcl_ctx *c) {
     const long long m = c->desc.n_drives;
+    if (c->exp) return (m + 1) * (m + 2) / 2 + c->x_dim * (m + 1);  // nothing involves X_{k+1}
     return (m + 1) * (m + 2) / 2 + 2 * c->x_dim * (m + 1);
 }
 static long long z_len(const pcl_ctx *c) {
@@ -343,11 +349,17 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 
 #include "pcl_host_variational.hpp"
 
-// The exponential mode (PCL_ORDER_EXP) serves the residual, the Jacobian, the rollout and the objective family.  The Hessian of the Lagrangian (its
-// (u_i, u_j) block needs second Frechet derivatives: DESIGN.md section 8), the compact Jacobian and the merit / reduce payload are refused in these words.
+// The exponential mode (PCL_ORDER_EXP) serves the residual, the Jacobian, the rollout and the objective family.  The compact Jacobian and the
+// merit / reduce payload are refused in these words, and so is the Hessian of the Lagrangian (its (u_i, u_j) block needs second Frechet
+// derivatives: pcl_kernel_exp_hess.hpp) unless the context's option exp_hess is on.
 #define EXP_NOTIMPL(ctx, what)                                                                                                                      \
     do {                                                                                                                                            \
         if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
+    } while (0)
+
+#define EXP_HESS_GATE(ctx, what)                       \
+    do {                                               \
+        if ((ctx) && !(ctx)->exp_hess) EXP_NOTIMPL(ctx, what); \
     } while (0)
 
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
@@ -651,7 +663,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);
@@ -722,7 +734,7 @@ extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *pe
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    EXP_NOTIMPL(ctx, "pcl_hess_nnz");
+    EXP_HESS_GATE(ctx, "pcl_hess_nnz");
     if (per) *per = hess_per(ctx);
     if (nnz) *nnz = hess_per(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
@@ -791,7 +803,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
-    EXP_NOTIMPL(ctx, "pcl_hess_structure");
+    EXP_HESS_GATE(ctx, "pcl_hess_structure");
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
     const long long m = D.n_drives, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
@@ -817,6 +829,7 @@ static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
             for (long long l = 0; l < m; ++l)
                 for (long long q = 0; q < xd; ++q) put(uk + l, xk + q);
             for (long long q = 0; q < xd; ++q) put(hk, xk + q);
+            if (ctx->exp) continue;  // (delta_k is X_{k+1} minus something: no second derivative involves X_{k+1})
             for (long long l = 0; l < m; ++l)
                 for (long long q = 0; q < xd; ++q) put(xn + q, uk + l);
             for (long long q = 0; q < xd; ++q) put(xn + q, hk);
@@ -1397,6 +1410,51 @@ static int launch_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
     return PCL_OK;
 }
 
+// The Hessian of the Lagrangian in the exponential mode (option exp_hess; pcl_kernel_exp_hess.hpp): five rotating n x n tiles and the
+// reduction words; G(u_k) takes a sixth tile where that fits.  *g_lds: whether it does.  Returns the bytes of LDS the kernel needs.
+static size_t exp_hess_lds_bytes(const pcl_ctx *ctx, int *g_lds) {
+    const size_t tile = (size_t)lds_ld(ctx->n) * ctx->n, five = (5 * tile + 16) * sizeof(double);
+    const bool six = five + tile * sizeof(double) <= (size_t)ctx->max_lds;
+    if (g_lds) *g_lds = six ? 1 : 0;
+    return six ? five + tile * sizeof(double) : five;
+}
+static int exp_hess_fits(const pcl_ctx *ctx, const char *who) {
+    const size_t lds = exp_hess_lds_bytes(ctx, nullptr);
+    if (lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "%s: the exponential Hessian kernel needs %zu B of LDS (> %d) for n=%d: five n x n tiles of %zu B (served up to n = 62)", who, lds, ctx->max_lds,
+                    ctx->n, (size_t)lds_ld(ctx->n) * ctx->n * sizeof(double));
+    return PCL_OK;
+}
+static int launch_exp_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    if (int rc = exp_hess_fits(ctx, "pcl_hess")) return rc;
+    KParams p;
+    fill_params(ctx, p);
+    p.Z = Z + (ctx->desc.batch_mode == PCL_BATCH_TRAJ ? (long long)ctx->win_first * ctx->desc.z_dim * ctx->desc.N : 0);
+    p.mu = mu;
+    p.hess = hess;
+    int g_lds = 0;
+    const size_t lds = exp_hess_lds_bytes(ctx, &g_lds);
+    const long long items = (long long)p.batch * p.K, grid = items * std::max(p.m, 1);
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    const long long per = 2LL * p.n * p.n + 2, cap = (long long)ctx->desc.batch * ctx->K * per;
+    if (ctx->exph_cap < cap) {
+        if (ctx->dexph) (void)hipFree(ctx->dexph);
+        ctx->dexph = nullptr, ctx->exph_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dexph, (size_t)cap * sizeof(double)));
+        ctx->exph_cap = cap;
+    }
+    const size_t lds_prep = ((size_t)p.LD * p.n + 32 + 64 + 2 * (size_t)p.n * p.cols) * sizeof(double);  // G(u_k), the drives, the column sums, X_k and M
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_exp_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+    hipLaunchKernelGGL(pcl_exp_hess_prep_kernel, dim3((unsigned)items), dim3(256), lds_prep, ctx->stream, p, ctx->dexph);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_exp_hess_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned threads = p.n > 32 ? 512 : 256;  // (as the Jacobian kernel: a pair of output tiles per wave)
+    hipLaunchKernelGGL(pcl_exp_hess_kernel, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, p, (const double *)ctx->dGjd, (const double *)ctx->dexph, g_lds);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_hess_kernel = 100;  // the exponential Hessian kernel
+    return PCL_OK;
+}
+
 static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where);
 static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *jac, bool compact) {
     ON_DEVICE(ctx);
@@ -1683,7 +1741,8 @@ static size_t hess2_lds_bytes(const KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
-    EXP_NOTIMPL(ctx, "pcl_hess");
+    EXP_HESS_GATE(ctx, "pcl_hess");
+    if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);
     if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);
     if (int rc = resolve_order(ctx, nullptr, "pcl_hess")) return rc;
     KParams p;
@@ -2489,7 +2548,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
-    EXP_NOTIMPL(ctx, "pcl_hess");
+    EXP_HESS_GATE(ctx, "pcl_hess");
     ON_DEVICE(ctx);
     TRY(resolve_order(ctx, Z, "pcl_hess"));
     const long long nv = hess_per(ctx) * ctx->win_count * ctx->K;

@@ -55,10 +55,12 @@ class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
-                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0):  # fmt: skip
+                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False):  # fmt: skip
+        pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
+        if exp_hessian and pade_order != _lib.PCL_ORDER_EXP:
+            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         self._L = _lib.load()
         self._h = None
-        pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         n = d if state_cols == _lib.PCL_STATE_VECTOR else 2 * d  # PCL_STATE_VECTOR: general d x d generator, one column
         g0 = _colmajor(G0)
         gj = _colmajor(Gj) if m else np.zeros(1)
@@ -87,9 +89,13 @@ class _PclContext:
         self.x_dim, self.n_rows, self.n_cols = a.value, b.value, c.value
         self._chk(self._L.pcl_jac_nnz(h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz, self.jac_per = a.value, b.value
-        # the exponential constraint: no Hessian of the Lagrangian and no compact Jacobian (hess_structure / hess raise with the library's message)
+        # the exponential constraint: no compact Jacobian, and no Hessian of the Lagrangian (hess_structure / hess raise with the library's
+        # message) unless ``exp_hessian`` switches the library's option exp_hess on
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
-        if self.exponential:
+        self.exp_hessian = bool(exp_hessian)
+        if self.exp_hessian:
+            self.set_option("exp_hess", 1)
+        if self.exponential and not self.exp_hessian:
             self.hess_nnz = self.hess_per = 0
         else:
             self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
@@ -244,7 +250,10 @@ class _PclContext:
         self.n_rows = b.value
         self._chk(self._L.pcl_jac_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz = a.value
-        if self.exponential:  # (no Hessian of the Lagrangian, no compact Jacobian)
+        if self.exp_hessian:
+            self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.hess_nnz = a.value
+        if self.exponential:  # (no compact Jacobian; the Hessian of the Lagrangian by ``exp_hessian`` only)
             return
         self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.hess_nnz = a.value
@@ -454,14 +463,18 @@ class HipPadeIntegrator:
     in order -- the row order here is identical: member-major).
     """
 
-    def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10):
+    def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
         pointers, the scalar form ``f`` -- evaluates one order from the first call on.  ``pade_order=2..10`` pins the order
         (BASELINE.json's metric is quoted on 4, which deviates from the exp constraint by 1.6e-5 at config 3).  ``pade_order="exp"`` (or -1):
         the exponential constraint itself, ``x_{k+1} - exp(dt_k G(u_k)) x_k`` -- for steps too large for order 10 (``order_tol_met`` False); residual
-        and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own."""
+        and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own.
+        ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served too
+        (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62."""
+        if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
+            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         x_names = [x_name] if isinstance(x_name, str) else list(x_name)
         G_drives = np.asarray(G_drives, dtype=np.float64)
         G_drift = np.asarray(G_drift, dtype=np.float64)
@@ -497,7 +510,7 @@ class HipPadeIntegrator:
             dt_off=traj.components[traj.timestep].start, x_offs=[traj.components[nm].start for nm in x_names],
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
-            state_cols=_lib.PCL_STATE_VECTOR if vec else cols,
+            state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian,
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
