@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256) void pcl_reg_hess_kernel(const double *__restr
         for (int i = tid; i < R.dim; i += 256) {
             const double v = z[R.off + i], ri = Rv[R.r0 + i];
             o[i] = sigma * wv * ri;
-            if (R.pw >= 1) o[R.dim + i] = sigma * (R.pw == 1 ? 1.0 : 2.0 * h) * ri * v;
+            // v_i is dt itself: the mixed entry lies on (dt, dt), where both orders of the partial meet
+            if (R.pw >= 1) o[R.dim + i] = sigma * (R.pw == 1 ? 1.0 : 2.0 * h) * ri * v * (R.off + i == dt_off ? 2.0 : 1.0);
             s += ri * v * v;
         }
         if (R.pw == 2) {
