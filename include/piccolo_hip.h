@@ -87,7 +87,7 @@ typedef enum pcl_status {
  *     delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k
  * -- the reference's own (docs/src/concepts/index.md:21) -- for steps too large for order 10 (the order policy's order_tol_met = 0).  Chosen at
  * creation only; nothing switches to it on its own.  Shapes: unitary, ket, PCL_STATE_VECTOR; PCL_BATCH_MEMBERS (shared or per-member G0) and
- * PCL_BATCH_TRAJ with the member window; m = 0; PCL_BATCH_VARIATIONAL: PCL_ENOTIMPL.  Rows as always.  Jacobian values per (member b, interval k),
+ * PCL_BATCH_TRAJ with the member window; m = 0; PCL_BATCH_VARIATIONAL: PCL_ENOTIMPL (the variational integrators take it as PCL_BATCH_VARIATIONAL_EXP).  Rows as always.  Jacobian values per (member b, interval k),
  * jac_nnz_per_interval = cols*n*n + x_dim*(m + 2) doubles (reported by pcl_jac_structure, never assumed), E = exp(h G), L_l the Frechet derivative
  * of exp at h G along h G_l:
  *     seg 0  d delta/d X_k      for c<cols, j<n, i<n : -E[i,j]   row c*n+i, col x_off + c*n+j     (knot k)
@@ -146,6 +146,32 @@ typedef enum pcl_status {
                                reduce entry points, the member window and the compact Jacobian stay PCL_ENOTIMPL whatever the option says.
                                The sensitivity term is evaluated at the TERMINAL knot only (the reference's own use, materialize.jl:306-307). */
 
+#define PCL_BATCH_VARIATIONAL_EXP 3 /* the same integrators on the EXACT exponential constraint x'_{k+1} = exp(dt_k Ghat) x'_k of the lifted generator
+                               Ghat = var_G(G(u), [Gv_i]) -- what the reference's VariationalUnitaryIntegrator / VariationalKetIntegrator are
+                               (BilinearIntegrator(var_G(..))) -- for the steps whose lifted theta no Pade order follows.  The descriptor of
+                               PCL_BATCH_VARIATIONAL (batch = 1 + v with v = 1, 2, x_offs per component, per_member_G0 = 1, state_cols d or 1,
+                               rows knot-major over the stacked state) with pade_order = PCL_ORDER_EXP; any other order: PCL_EINVAL.  Generator
+                               dimension n <= 62 (five n x n LDS tiles; beyond: PCL_ESHAPE with the byte counts, from pcl_create).  With h = dt_k,
+                               A = h G(u_k), E = exp(A), L_i = L(A; h Gv_i), L_l = L(A; h G_l) (Frechet derivatives of exp) and
+                               L2_il = L2(A; h Gv_i, h G_l) (the second one):
+                                 delta_0 = X_{k+1} - E X_k            delta_i = Xv_{i,k+1} - L_i X_k - E Xv_{i,k}
+                               Jacobian values per interval (pcl_jac_structure reports them; never assumed):
+                                 -E of delta_0 w.r.t. X_k (C n^2, I_C (x) .); per variation i: -E w.r.t. Xv_i,k, then -L_i w.r.t. X_k;
+                                 then +1 for r < x_dim' = (1 + v) n C (d delta / d X'_{k+1}, the identity as its diagonal); then the tails,
+                                 component-major, per state column c: for l<m the n values of column u_off + l, then the n of column dt_off:
+                                   component 0: -(L_l X_k)[:,c]                     and -(G E X_k)[:,c]
+                                   component i: -(L2_il X_k + L_l Xv_i,k)[:,c]      and -((Gv_i E + G L_i) X_k + G E Xv_i,k)[:,c]
+                               -- (1 + 2v) C n^2 + x_dim' (m + 2) values, no structural zeros.  Served: create / destroy, dimensions,
+                               pcl_jac_nnz / _structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev] (host-pointer calls deliver
+                               full values), streams, sync, options, pcl_deriv_*; with option "var_full" = 1 the robust-control objective
+                               family and pcl_rollout[_dev] exactly as on a PCL_BATCH_VARIATIONAL context, with its bits.  PCL_ENOTIMPL, naming
+                               the mode: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64] and option "exp_hess" = 1 (the Hessian of the
+                               Lagrangian needs third Frechet derivatives: solve with a quasi-Newton Hessian), the compact Jacobian trio, the
+                               merit / reduce entry points, the member window, pcl_infidelity_dev.  pcl_set_order_policy and
+                               pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  "var_block_wgs" / "var_col_wgs" have no
+                               effect.  get_option "pade_order" reads -1, "variations" v, "last_kernel" 110 (residual + Jacobian) or 111
+                               (residual only). */
+
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
     int32_t d;           /* Hilbert-space dimension (sys.levels); n = 2d, x_dim = 2 d^2 */
@@ -155,7 +181,7 @@ typedef struct pcl_desc {
     int32_t u_off;       /* 0-based offset of the drive component inside a knot (traj.components[:u][1]-1) */
     int32_t dt_off;      /* 0-based offset of the timestep component */
     int32_t batch;       /* number of members / seeds (>= 1) */
-    int32_t batch_mode;  /* PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ or PCL_BATCH_VARIATIONAL */
+    int32_t batch_mode;  /* PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL or PCL_BATCH_VARIATIONAL_EXP */
     int32_t pade_order;  /* diagonal Pade order p of B^{+-}_p: 2, 4, 6, 8 or 10; 0: the smallest order whose deviation from the reference's
                             exp constraint is below a tolerance -- pcl_set_order_policy, or the first host-pointer call decides;
                             PCL_ORDER_EXP: the exponential constraint itself (see there) */

@@ -24,6 +24,8 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     }
     else if (!strcmp(key, "exp_hess")) {  // exponential contexts: serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "exp_hess must be 0 or 1");
+        if (v && ctx->vexp)
+            return fail(ctx, PCL_ENOTIMPL, "exp_hess = 1 is not implemented for a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): the Hessian of the Lagrangian needs third Frechet derivatives of exp; solve with a quasi-Newton Hessian");
         if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_hess = 1 needs a context of the exponential constraint (PCL_ORDER_EXP)");
         if (v) TRY(exp_hess_fits(ctx, "exp_hess = 1"));
         ctx->exp_hess = (int)v;

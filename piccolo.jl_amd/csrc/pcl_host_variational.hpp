@@ -4,9 +4,12 @@
 #pragma once
 #include "pcl_kernel_variational.hpp"
 #include "pcl_kernel_var_rollout.hpp"
+#include "pcl_kernel_var_exp.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
+// PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
 static long long var_jac_per(const pcl_ctx *c) {
+    if (c->vexp) return (1LL + 2LL * c->var) * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 2);
     return (2LL + 4LL * c->var) * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
 
@@ -22,7 +25,10 @@ static int var_validate(const pcl_desc *D) {
         return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=%d; PCL_BATCH_VARIATIONAL takes d (unitary, or 0) or 1 (ket)", D->state_cols);
     if (m < 0) return fail(nullptr, PCL_EINVAL, "pcl_create: n_drives=%d", m);
     if (D->N < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: N=%d; need N >= 2", D->N);
-    if (D->pade_order != 0 && D->pade_order != 2 && D->pade_order != 4 && D->pade_order != 6 && D->pade_order != 8 && D->pade_order != 10)
+    if (D->batch_mode == PCL_BATCH_VARIATIONAL_EXP) {
+        if (D->pade_order != PCL_ORDER_EXP)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: pade_order=%d with batch_mode = PCL_BATCH_VARIATIONAL_EXP; that batch_mode takes pade_order = PCL_ORDER_EXP (-1) only", D->pade_order);
+    } else if (D->pade_order != 0 && D->pade_order != 2 && D->pade_order != 4 && D->pade_order != 6 && D->pade_order != 8 && D->pade_order != 10)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order=%d; diagonal Pade orders 2, 4, 6, 8, 10 are implemented (0: chosen by pcl_set_order_policy)", D->pade_order);
     if (D->index_base != 0 && D->index_base != 1) return fail(nullptr, PCL_EINVAL, "pcl_create: index_base=%d; must be 0 or 1", D->index_base);
     if (D->global_dim < 0) return fail(nullptr, PCL_EINVAL, "pcl_create: global_dim=%lld", (long long)D->global_dim);
@@ -52,6 +58,14 @@ static int var_validate(const pcl_desc *D) {
     return PCL_OK;
 }
 
+// LDS of pcl_var_exp_kernel: five rotating n x n tiles, a sixth for G(u_k) where that fits (*g_lds).  (LD as lds_ld(n).)
+static size_t var_exp_lds_bytes(int n, size_t max_lds, int *g_lds) {
+    const size_t tile = (size_t)(((n + 3) & ~3) + 2) * n * sizeof(double), five = 5 * tile;
+    const bool six = five + tile <= max_lds;
+    if (g_lds) *g_lds = six ? 1 : 0;
+    return six ? five + tile : five;
+}
+
 static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (int rc = var_validate(dsc)) return rc;
     const int d = dsc->d, m = dsc->n_drives, n = 2 * d, v = dsc->batch - 1;
@@ -66,6 +80,7 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
     const size_t nn = (size_t)n * n;
     ctx->desc = *dsc;
     ctx->var = v;
+    ctx->vexp = dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP ? 1 : 0;
     ctx->n = n;
     ctx->K = dsc->N - 1;
     ctx->cols = cols;
@@ -122,6 +137,12 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
     }
     ctx->max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
     ctx->n_cu = prop.multiProcessorCount;
+    if (ctx->vexp && var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr) > (size_t)ctx->max_lds) {
+        fail(nullptr, PCL_ESHAPE, "pcl_create: PCL_BATCH_VARIATIONAL_EXP needs %zu B of LDS (> %d) for n=%d: five n x n tiles of %zu B (served up to n = 62)",
+             var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr), ctx->max_lds, n, var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr) / 5);
+        pcl_destroy(ctx);
+        return PCL_ESHAPE;
+    }
     VAR_HIP(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
     // row-compressed (ELL) tables of the column role, [slot t][row i], padded with column 0 / value 0: G(u) on the union pattern of the drift
@@ -202,13 +223,18 @@ static int var_jac_structure(const pcl_ctx *ctx, I *rows, I *cols) {
                     }
         };
         block(0, 0, 0);
-        block(0, 0, 1);
+        if (!ctx->vexp) block(0, 0, 1);
         for (int b = 1; b <= v; ++b) {
             block(b, b, 0);
-            block(b, b, 1);
+            if (!ctx->vexp) block(b, b, 1);
             block(b, 0, 0);
-            block(b, 0, 1);
+            if (!ctx->vexp) block(b, 0, 1);
         }
+        if (ctx->vexp)  // d delta / d X'_{k+1} = I: its diagonal, after the blocks
+            for (long long q = 0; q < xd; ++q, ++p) {
+                r[p] = (I)(k * xd + q + base);
+                c[p] = (I)((k + 1) * zd + ctx->x_offs[q / xdc] + q % xdc + base);
+            }
         for (int b = 0; b <= v; ++b)
             for (long long cc = 0; cc < C; ++cc)
                 for (long long l = 0; l <= m; ++l) {
@@ -343,8 +369,59 @@ static int var_split_cols(const pcl_ctx *ctx) {
     return std::max(1, std::min(a, C));
 }
 
+// PCL_BATCH_VARIATIONAL_EXP (pcl_kernel_var_exp.hpp): the preparation launch (G(u_k) and its norm per interval), then one workgroup per
+// (interval, variation, drive) for residual + Jacobian, per (interval, variation) for the residual alone.
+static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var;
+    const size_t nn = (size_t)n * n;
+    VarExpParams p;
+    memset(&p, 0, sizeof p);
+    int g_lds = 0;
+    const size_t lds = var_exp_lds_bytes(n, (size_t)ctx->max_lds, &g_lds);
+    const bool jac = vals != nullptr;
+    const long long grid = (long long)ctx->K * v * (jac ? std::max(m, 1) : 1);
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
+    const long long cap = (long long)ctx->K * ((long long)nn + 2);
+    if (ctx->exph_cap < cap) {
+        if (ctx->dexph) (void)hipFree(ctx->dexph);
+        ctx->dexph = nullptr, ctx->exph_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dexph, (size_t)cap * sizeof(double)));
+        ctx->exph_cap = cap;
+    }
+    p.Z = Z;
+    p.delta = delta;
+    p.vals = vals;
+    p.G0 = ctx->dvar_tab;
+    p.Gj = ctx->dvar_tab + nn;
+    p.Gv = ctx->dvar_tab + (1 + m) * nn;
+    p.ws = ctx->dexph;
+    p.jper = var_jac_per(ctx);
+    p.n = n;
+    p.LD = ((n + 3) & ~3) + 2;
+    p.cols = ctx->cols;
+    p.m = m;
+    p.K = ctx->K;
+    p.v = v;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.g_lds = g_lds;
+    for (int b = 0; b <= v; ++b) p.xo[b] = ctx->x_offs[b];
+    hipLaunchKernelGGL(pcl_var_exp_prep_kernel, dim3((unsigned)ctx->K), dim3(256), 0, ctx->stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    const void *f = jac ? (const void *)pcl_var_exp_kernel<true> : (const void *)pcl_var_exp_kernel<false>;
+    if (int rc = var_set_lds(ctx, f, lds)) return rc;
+    const unsigned threads = n > 32 ? 512 : 256;  // (as the exponential kernels: a pair of output tiles per wave)
+    void *args[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3(threads), args, lds, ctx->stream));
+    ctx->last_kernel = jac ? 110 : 111;
+    return PCL_OK;
+}
+
 static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
     ON_DEVICE(ctx);
+    if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals);
     if (ctx->desc.pade_order == 0)
         return fail(ctx, PCL_EINVAL, "pcl_eval / pcl_jac: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
     VarParams p;
@@ -403,12 +480,19 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
 
 #define VAR_NOTIMPL(ctx, what)                                                                                                         \
     do {                                                                                                                               \
-        if ((ctx) && (ctx)->var) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (PCL_BATCH_VARIATIONAL)", what); \
+        if ((ctx) && (ctx)->var)                                                                                                       \
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (%s)", what, (ctx)->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL"); \
     } while (0)
 // The objective and the rollout: refused in the same words unless the context's option var_full is on (pcl_host_robust.hpp serves them then).
 #define VAR_GATE(ctx, what)                                        \
     do {                                                           \
         if ((ctx) && (ctx)->var && !(ctx)->var_full) VAR_NOTIMPL(ctx, what); \
+    } while (0)
+// The Hessian of the Lagrangian of PCL_BATCH_VARIATIONAL_EXP: its (u_i, u_j) block on component i needs third Frechet derivatives of exp.
+#define VAR_EXP_NOHESS(ctx, what)                                                                                                                                   \
+    do {                                                                                                                                                            \
+        if ((ctx) && (ctx)->vexp)                                                                                                                                   \
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): the Hessian of the Lagrangian needs third Frechet derivatives of exp; solve with a quasi-Newton Hessian", what); \
     } while (0)
 static int var_set_full(pcl_ctx *ctx, int64_t on);
 static int var_set_goal(pcl_ctx *ctx, const double *goal_iso_vec);

@@ -10,6 +10,7 @@
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
 //   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
 //   pcl_kernel_exp_hess.hpp    ... its Hessian of the Lagrangian (option exp_hess): second Frechet derivatives, one chain per drive
+//   pcl_kernel_var_exp.hpp     the variational integrators on the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): residual and Jacobian
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -66,6 +67,7 @@ struct pcl_ctx {
     double *dexph = nullptr;     // ... its workspace: [G(u_k) | W_k | norm] per (member, interval)
     long long exph_cap = 0;
     int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
+    int vexp = 0;           // ... PCL_BATCH_VARIATIONAL_EXP: the exponential constraint on the lifted generator (pcl_kernel_var_exp.hpp; its workspace is dexph)
     long long var_xdc = 0;  // ... x_dim of one component
     int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
     double *dvar_tab = nullptr;  // ... [G_drift | G_l | Gv_i | the same transposed], n x n column-major each
@@ -370,8 +372,8 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL && dsc->pade_order == PCL_ORDER_EXP)
-        return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented");
-    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL) return var_create(dsc, out);
+        return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented; use batch_mode = PCL_BATCH_VARIATIONAL_EXP");
+    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP) return var_create(dsc, out);
     const bool vec = dsc->state_cols == PCL_STATE_VECTOR;  // general real d x d generator on one real column
     const int d = dsc->d, m = dsc->n_drives, n = vec ? d : 2 * d;
     if (d < 1 || m < 0 || dsc->N < 2 || dsc->batch < 1)
@@ -734,6 +736,7 @@ extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *pe
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
+    VAR_EXP_NOHESS(ctx, "pcl_hess_nnz");
     EXP_HESS_GATE(ctx, "pcl_hess_nnz");
     if (per) *per = hess_per(ctx);
     if (nnz) *nnz = hess_per(ctx) * ctx->win_count * ctx->K;
@@ -803,6 +806,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
+    VAR_EXP_NOHESS(ctx, "pcl_hess_structure");
     EXP_HESS_GATE(ctx, "pcl_hess_structure");
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
@@ -1460,7 +1464,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_eval / pcl_jac")) return rc;
     if (ctx->var) {
-        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (PCL_BATCH_VARIATIONAL)");
+        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (%s)", ctx->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL");
         return var_launch_fused(ctx, Z, delta, jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
@@ -1741,6 +1745,7 @@ static size_t hess2_lds_bytes(const KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
+    VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);
     if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);
@@ -2241,7 +2246,7 @@ extern "C" int pcl_order_for_bounds(int32_t n, int32_t m, const double *G0, int3
 }
 extern "C" int pcl_set_order_policy(pcl_ctx *ctx, double dt_max, const double *u_max, double tol, int32_t *order_out) {
     if (!ctx) return PCL_EINVAL;
-    if (ctx->exp) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: the context evaluates the exponential constraint; there is no order to choose");
+    if (ctx->exp || ctx->vexp) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: the context evaluates the exponential constraint; there is no order to choose");
     if (!(dt_max > 0.0) || !(tol > 0.0) || (ctx->desc.n_drives > 0 && !u_max)) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: need dt_max > 0, tol > 0 and the drives' bounds");
 #ifdef PCL_LAB
     if (ctx->res.active) return fail(ctx, PCL_EINVAL, "pcl_set_order_policy: a resident evaluator is running (pcl_resident_stop first)");
@@ -2287,7 +2292,7 @@ static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where) 
 
 extern "C" int pcl_set_order_from_trajectory(pcl_ctx *ctx, const double *Z_host, double tol, int32_t *order_out) {
     if (!ctx) return PCL_EINVAL;
-    if (ctx->exp) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: the context evaluates the exponential constraint; there is no order to choose");
+    if (ctx->exp || ctx->vexp) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: the context evaluates the exponential constraint; there is no order to choose");
     if (!Z_host) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: NULL trajectory");
 #ifdef PCL_LAB
     if (ctx->res.active) return fail(ctx, PCL_EINVAL, "pcl_set_order_from_trajectory: a resident evaluator is running (pcl_resident_stop first)");
@@ -2548,6 +2553,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
+    VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     ON_DEVICE(ctx);
     TRY(resolve_order(ctx, Z, "pcl_hess"));

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL, PclError
+from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP, PclError
 from .trajectory import STATE, TIMESTEP, NamedTrajectory
 
 __all__ = [
@@ -100,7 +100,7 @@ class _PclContext:
         else:
             self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
-        if batch_mode == PCL_BATCH_VARIATIONAL or self.exponential:  # (no compact Jacobian for the stacked state)
+        if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) or self.exponential:  # (no compact Jacobian for the stacked state)
             self.compact_nnz = self.compact_per = 0
         else:
             self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
@@ -108,7 +108,7 @@ class _PclContext:
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
         self.window = (0, batch)
         # a variational context: x_dim is the stacked state; goals and forms speak of component 0, the rollout returns one stacked trajectory
-        self.variational = batch_mode == PCL_BATCH_VARIATIONAL
+        self.variational = batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
         self.goal_dim = self.x_dim // batch if self.variational else self.x_dim
 
     def _chk(self, rc):
@@ -557,7 +557,12 @@ class HipVariationalIntegrator:
     """Drop-in for the ``BilinearIntegrator`` the reference's variational constructors build [REF src/control/integrators.jl:234-264]: the state
     ``vcat(x, x_var_1, ..., x_var_v)`` evolved by ``var_G(G(u), [Gv_i])`` per state column, ``Gv_i = G(H_var_i) / scale_i``.  One context of
     batch_mode PCL_BATCH_VARIATIONAL; rows are knot-major over the stacked state (``B.dim = B.x_dim * (N - 1)``).  Build it with
-    ``VariationalUnitaryIntegrator`` or ``VariationalKetIntegrator``."""
+    ``VariationalUnitaryIntegrator`` or ``VariationalKetIntegrator``.
+
+    ``pade_order="exp"`` (or -1): the reference's own constraint ``x'_{k+1} = exp(dt_k var_G(..)) x'_k`` instead of a Pade discretisation of
+    it -- a context of batch_mode PCL_BATCH_VARIATIONAL_EXP, for the steps whose lifted ``theta`` no Pade order follows.  Residual, Jacobian,
+    objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
+    derivatives: solve with a quasi-Newton Hessian)."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10):
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
@@ -585,10 +590,12 @@ class HipVariationalIntegrator:
         self.G_drives = np.asarray(sys.G_drives_array(), dtype=np.float64).reshape(m, n, n)
         self.G_vars = np.asarray(Gv, dtype=np.float64).reshape(len(Gv), n, n)
         self._sig = (traj.dim, traj.N)
+        pade_order = _lib.order_code(pade_order)
+        self.exponential = pade_order == _lib.PCL_ORDER_EXP
         self._ctx = _PclContext(
             d=sys.levels, m=m, N=traj.N, z_dim=traj.dim, u_off=traj.components[u_name].start, dt_off=traj.components[traj.timestep].start,
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
-            batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
+            batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols,
         )  # fmt: skip
         if pade_order == 0:

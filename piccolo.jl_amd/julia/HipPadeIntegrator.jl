@@ -263,8 +263,13 @@ end
 # ---- variational (sensitivity) integrators: batch_mode PCL_BATCH_VARIATIONAL (= 2) -- ONE context over the stacked state
 #      vcat(x, x_var_1, ...), generator var_G(G(u), [G_var_i / scale_i]); rows knot-major over the stacked state (B.dim = x_dim (N - 1)).
 #      The member window does not exist for this mode: the structure is queried whole.
+#      pade_order = :exp (or PCL_ORDER_EXP = -1): batch_mode PCL_BATCH_VARIATIONAL_EXP (= 3), the reference's own constraint
+#      x'_{k+1} = exp(dt_k var_G(..)) x'_k on the stacked state -- residual, Jacobian, objective and rollout; no Hessian of the Lagrangian
+#      (third Frechet derivatives: the structure stays empty, solve with eval_hessian = false).
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
-                      device::Integer = 0, pade_order::Integer = 0, order_tol::Float64 = 1e-10)
+                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10)
+    pade_order = _order_code(pade_order)
+    expo = pade_order == PCL_ORDER_EXP
     m = sys.n_drives
     e(j) = (a = zeros(m); a[j] = 1.0; a)
     zu = zeros(m)
@@ -278,7 +283,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve G0s Gjv x_offs begin
         desc = PclDesc(sizeof(PclDesc), size(G0, 1) ÷ 2, m, traj.N, traj.dim, traj.components[u][1] - 1, traj.components[traj.timestep][1] - 1,
-                       length(names), 2 #= PCL_BATCH_VARIATIONAL =#, pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
+                       length(names), expo ? 3 #= PCL_BATCH_VARIATIONAL_EXP =# : 2 #= PCL_BATCH_VARIATIONAL =#, pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
                        state_cols, traj.global_dim, pointer(G0s), pointer(Gjv), pointer(x_offs))
         rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
         rc == 0 || error("pcl_create: ", _lasterr(C_NULL))
@@ -287,7 +292,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     xd = Ref{Int64}(0); nr = Ref{Int64}(0); ncol = Ref{Int64}(0); nnz = Ref{Int64}(0); per = Ref{Int64}(0); hnnz = Ref{Int64}(0)
     check(c, ccall((:pcl_constraint_dim, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), c, xd, nr, ncol))
     check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
-    check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    expo ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
@@ -296,7 +301,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
     check(c, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, jr, jc))
     hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
-    check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
+    expo || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
     # (B.f is refused for the stacked state, see _f: fcore stays `nothing`)
     return HipPadeIntegrator(core, 1, x, names, u, core.x_dim, core.rows_per, jr, jc, hr, hc, Int(ncol[]), G0, Gj, state_cols, order, nothing)
 end
