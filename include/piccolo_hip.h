@@ -166,7 +166,8 @@ typedef enum pcl_status {
                                full values), streams, sync, options, pcl_deriv_*; with option "var_full" = 1 the robust-control objective
                                family and pcl_rollout[_dev] exactly as on a PCL_BATCH_VARIATIONAL context, with its bits.  PCL_ENOTIMPL, naming
                                the mode: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64] and option "exp_hess" = 1 (the Hessian of the
-                               Lagrangian needs third Frechet derivatives: solve with a quasi-Newton Hessian), the compact Jacobian trio, the
+                               Lagrangian needs third Frechet derivatives: solve with a quasi-Newton Hessian) unless option "var_exp_hess" = 1
+                               is set (generator dimensions up to 44; see pcl_hess), the compact Jacobian trio, the
                                merit / reduce entry points, the member window, pcl_infidelity_dev.  pcl_set_order_policy and
                                pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  "var_block_wgs" / "var_col_wgs" have no
                                effect.  get_option "pade_order" reads -1, "variations" v, "last_kernel" 110 (residual + Jacobian) or 111
@@ -243,7 +244,13 @@ int pcl_hess_structure_i64(const pcl_ctx *ctx, int64_t *rows, int64_t *cols);
 int pcl_eval(pcl_ctx *ctx, const double *Z, double *delta);
 int pcl_jac(pcl_ctx *ctx, const double *Z, double *vals);
 int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *vals);
-/* mu: n_rows multipliers; vals: hess nnz. (sigma * objective Hessian is the objective's business.) */
+/* mu: n_rows multipliers; vals: hess nnz. (sigma * objective Hessian is the objective's business.)
+ * A PCL_BATCH_VARIATIONAL_EXP context serves pcl_hess[_dev], pcl_hess_nnz and pcl_hess_structure[_i64] only with
+ * pcl_set_option(ctx, "var_exp_hess", 1) (0, the default: PCL_ENOTIMPL in the words above): the Hessian of the Lagrangian of the exact lifted
+ * constraint, third Frechet derivatives of exp through an octuple chain per (interval, variation, drive).  Values per interval:
+ * (m+1)(m+2)/2 + x_dim'*(m+1), x_dim' the stacked state -- the Pade variational layout without its two X'_{k+1} groups, from pcl_hess_structure
+ * as always.  Generator dimensions up to n = 44 (nine LDS tiles); beyond, setting the option is PCL_ESHAPE with the byte counts and the
+ * context goes on as before.  Two launches give the same bits.  Get "last_hess_kernel" reads 110 after such a launch. */
 int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals);
 
 /* device-pointer evaluation (asynchronous on the context's stream; results stay in HBM) ---- */

@@ -30,6 +30,13 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v) TRY(exp_hess_fits(ctx, "exp_hess = 1"));
         ctx->exp_hess = (int)v;
     }
+    else if (!strcmp(key, "var_exp_hess")) {  // variational contexts of the exponential constraint: serve the Hessian of the Lagrangian (0: refuse it, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_exp_hess must be 0 or 1");
+        if (v)
+            TRY(var_exp_hess_enable(ctx));
+        else
+            ctx->var_exp_hess = 0;
+    }
 #ifdef PCL_PROFILE
     else if (!strcmp(key, "profile_flags"))  // profiling experiments (results may be WRONG); not present in the shipped library
         ctx->opt_prof = v;
@@ -167,6 +174,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->var_full;
     else if (!strcmp(key, "exp_hess"))
         *v = ctx->exp_hess;
+    else if (!strcmp(key, "var_exp_hess"))
+        *v = ctx->var_exp_hess;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

@@ -5,6 +5,7 @@
 #include "pcl_kernel_variational.hpp"
 #include "pcl_kernel_var_rollout.hpp"
 #include "pcl_kernel_var_exp.hpp"
+#include "pcl_kernel_var_exp_hess.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
@@ -249,6 +250,7 @@ static int var_jac_structure(const pcl_ctx *ctx, I *rows, I *cols) {
 }
 
 // Today's segment order (pcl_hess_structure) over the stacked state: entry q of the state is component q / x_dim, offset q % x_dim.
+// PCL_BATCH_VARIATIONAL_EXP (option var_exp_hess): the first five segments -- nothing involves X'_{k+1}.
 template <class I>
 static int var_hess_structure(const pcl_ctx *ctx, I *rows, I *cols) {
     const pcl_desc &D = ctx->desc;
@@ -271,6 +273,7 @@ static int var_hess_structure(const pcl_ctx *ctx, I *rows, I *cols) {
         for (long long l = 0; l < m; ++l)
             for (long long q = 0; q < xd; ++q) put(uk + l, xk(q, 0));
         for (long long q = 0; q < xd; ++q) put(hk, xk(q, 0));
+        if (ctx->vexp) continue;
         for (long long l = 0; l < m; ++l)
             for (long long q = 0; q < xd; ++q) put(xk(q, 1), uk + l);
         for (long long q = 0; q < xd; ++q) put(xk(q, 1), hk);
@@ -419,6 +422,96 @@ static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *
     return PCL_OK;
 }
 
+// The Hessian of the Lagrangian of PCL_BATCH_VARIATIONAL_EXP (option var_exp_hess; pcl_kernel_var_exp_hess.hpp).  The octuple kernel rotates nine
+// n x LD tiles (eight and the scratch) and G(u_k) takes a tenth where that fits; the quadruple kernel five, a sixth, and its reduction words.
+static int lds_ld(int n);
+static size_t var_exp_hess_tile_bytes(const pcl_ctx *ctx) { return (size_t)lds_ld(ctx->n) * ctx->n * sizeof(double); }
+static size_t var_exp_hess_lds_bytes(const pcl_ctx *ctx, bool oct, int *g_lds) {
+    const size_t tile = var_exp_hess_tile_bytes(ctx), base = oct ? 9 * tile : 5 * tile + 16 * sizeof(double);
+    const bool g = base + tile <= (size_t)ctx->max_lds;
+    if (g_lds) *g_lds = g ? 1 : 0;
+    return g ? base + tile : base;
+}
+static long long var_exp_hess_part_per(const pcl_ctx *ctx) {
+    const long long m = ctx->desc.n_drives;
+    return (m + 1) * (m + 2) / 2 + (m + 1) * ctx->var_xdc;
+}
+// option var_exp_hess = 1: the shape check, then the workspace (allocated here, on first use, not by pcl_create)
+static int var_exp_hess_enable(pcl_ctx *ctx) {
+    if (!ctx->vexp) return fail(ctx, PCL_EINVAL, "var_exp_hess = 1 needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)");
+    const size_t need = var_exp_hess_lds_bytes(ctx, true, nullptr);
+    if (need > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1: the octuple chain of third Frechet derivatives needs %zu B of LDS (> %d) for n=%d: nine n x n tiles of %zu B (a plan with tiles in the workspace is not built)",
+                    need, ctx->max_lds, ctx->n, var_exp_hess_tile_bytes(ctx));
+    // the last phase keeps two n x cols products per spent tile, and N_0 .. N_v in three pieces
+    if (2 * ctx->cols > ctx->n || ctx->var > 2)
+        return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1: %d state columns and %d variations; the kernel's last phase takes cols <= n / 2 = %d and at most 2 variations", ctx->cols, ctx->var, ctx->n / 2);
+    if (!ctx->dvexph) {
+        ON_DEVICE(ctx);
+        const size_t nn = (size_t)ctx->n * ctx->n;
+        const size_t ws = (size_t)ctx->K * ((2 + ctx->var) * nn + 2), part = (size_t)ctx->K * (1 + ctx->var) * (size_t)var_exp_hess_part_per(ctx);
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dvexph, ws * sizeof(double)));
+        hipError_t e = hipMalloc((void **)&ctx->dvexph_part, part * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipFree(ctx->dvexph);
+            ctx->dvexph = nullptr;
+            HIP_TRY(ctx, e);
+        }
+    }
+    ctx->var_exp_hess = 1;
+    return PCL_OK;
+}
+static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    ON_DEVICE(ctx);
+    if (!ctx->var_exp_hess || !ctx->dvexph) return fail(ctx, PCL_EINVAL, "pcl_hess: option var_exp_hess is off");
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var, ml = std::max(m, 1);
+    const size_t nn = (size_t)n * n;
+    VarExpHessParams p;
+    memset(&p, 0, sizeof p);
+    int g_quad = 0, g_oct = 0;
+    const size_t lds_quad = var_exp_hess_lds_bytes(ctx, false, &g_quad), lds_oct = var_exp_hess_lds_bytes(ctx, true, &g_oct);
+    const long long grid = (long long)ctx->K * v * ml;
+    p.pper = var_exp_hess_part_per(ctx);
+    const long long fin = ((long long)ctx->K * p.pper + 255) / 256;
+    if (grid > 0x7fffffffLL || fin > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_hess: %lld workgroups exceed the grid limit", std::max(grid, fin));
+    p.Z = Z;
+    p.mu = mu;
+    p.hess = hess;
+    p.G0 = ctx->dvar_tab;
+    p.Gj = ctx->dvar_tab + nn;
+    p.Gv = ctx->dvar_tab + (1 + m) * nn;
+    p.ws = ctx->dvexph;
+    p.part = ctx->dvexph_part;
+    p.hper = hess_per(ctx);
+    p.wsper = (2LL + v) * (long long)nn + 2;
+    p.n = n;
+    p.LD = lds_ld(n);
+    p.cols = ctx->cols;
+    p.m = m;
+    p.K = ctx->K;
+    p.v = v;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    for (int b = 0; b <= v; ++b) p.xo[b] = ctx->x_offs[b];
+    const size_t lds_prep = (nn + 32 + 64 + 2 * (size_t)(1 + v) * ctx->var_xdc) * sizeof(double);  // G(u_k), the drives, the column sums, X'_k and M'
+    if (int rc = var_set_lds(ctx, (const void *)pcl_var_exp_hess_prep_kernel, lds_prep)) return rc;
+    void *args[] = {&p};
+    HIP_TRY(ctx, hipLaunchKernel((const void *)pcl_var_exp_hess_prep_kernel, dim3((unsigned)ctx->K), dim3(256), args, lds_prep, ctx->stream));
+    const unsigned threads = n > 32 ? 512 : 256;  // (as the sibling kernels: a pair of output tiles per wave)
+    const void *fq = (const void *)pcl_var_exp_hess_kernel<false>, *fo = (const void *)pcl_var_exp_hess_kernel<true>;
+    if (int rc = var_set_lds(ctx, fq, lds_quad)) return rc;
+    if (int rc = var_set_lds(ctx, fo, lds_oct)) return rc;
+    p.g_lds = g_quad;
+    HIP_TRY(ctx, hipLaunchKernel(fq, dim3((unsigned)(ctx->K * ml)), dim3(threads), args, lds_quad, ctx->stream));
+    p.g_lds = g_oct;
+    HIP_TRY(ctx, hipLaunchKernel(fo, dim3((unsigned)grid), dim3(threads), args, lds_oct, ctx->stream));
+    HIP_TRY(ctx, hipLaunchKernel((const void *)pcl_var_exp_hess_finish_kernel, dim3((unsigned)fin), dim3(256), args, 0, ctx->stream));
+    ctx->last_hess_kernel = 110;
+    return PCL_OK;
+}
+
 static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
     ON_DEVICE(ctx);
     if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals);
@@ -489,9 +582,10 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
         if ((ctx) && (ctx)->var && !(ctx)->var_full) VAR_NOTIMPL(ctx, what); \
     } while (0)
 // The Hessian of the Lagrangian of PCL_BATCH_VARIATIONAL_EXP: its (u_i, u_j) block on component i needs third Frechet derivatives of exp.
+// Refused in these words unless the context's option var_exp_hess is on (var_exp_launch_hess serves it then).
 #define VAR_EXP_NOHESS(ctx, what)                                                                                                                                   \
     do {                                                                                                                                                            \
-        if ((ctx) && (ctx)->vexp)                                                                                                                                   \
+        if ((ctx) && (ctx)->vexp && !(ctx)->var_exp_hess)                                                                                                           \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): the Hessian of the Lagrangian needs third Frechet derivatives of exp; solve with a quasi-Newton Hessian", what); \
     } while (0)
 static int var_set_full(pcl_ctx *ctx, int64_t on);

@@ -10,6 +10,7 @@
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
 //   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
 //   pcl_kernel_exp_hess.hpp    ... its Hessian of the Lagrangian (option exp_hess): second Frechet derivatives, one chain per drive
+//   pcl_kernel_var_exp_hess.hpp ... the same of a variational context (option var_exp_hess): third Frechet derivatives, an octuple chain per (variation, drive)
 //   pcl_kernel_var_exp.hpp     the variational integrators on the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): residual and Jacobian
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
@@ -68,6 +69,8 @@ struct pcl_ctx {
     long long exph_cap = 0;
     int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
     int vexp = 0;           // ... PCL_BATCH_VARIATIONAL_EXP: the exponential constraint on the lifted generator (pcl_kernel_var_exp.hpp; its workspace is dexph)
+    int var_exp_hess = 0;   // ... ... option var_exp_hess: its Hessian of the Lagrangian is served (pcl_kernel_var_exp_hess.hpp)
+    double *dvexph = nullptr, *dvexph_part = nullptr;  // ... ... that launch's workspace [G(u_k) | norm | W_0 | W_i] and partial sums, per interval
     long long var_xdc = 0;  // ... x_dim of one component
     int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
     double *dvar_tab = nullptr;  // ... [G_drift | G_l | Gv_i | the same transposed], n x n column-major each
@@ -328,7 +331,7 @@ static long long jac_per_full(const pcl_ctx *c) {
 static long long jac_per_compact(const pcl_ctx *c) { return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1); }
 static long long hess_per(const pcl_ctx *c) {
     const long long m = c->desc.n_drives;
-    if (c->exp) return (m + 1) * (m + 2) / 2 + c->x_dim * (m + 1);  // nothing involves X_{k+1}
+    if (c->exp || c->vexp) return (m + 1) * (m + 2) / 2 + c->x_dim * (m + 1);  // nothing involves X_{k+1}
     return (m + 1) * (m + 2) / 2 + 2 * c->x_dim * (m + 1);
 }
 static long long z_len(const pcl_ctx *c) {
@@ -665,7 +668,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);
@@ -1748,6 +1751,7 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
     VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);
+    if (ctx->vexp) return var_exp_launch_hess(ctx, Z, mu, hess);
     if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);
     if (int rc = resolve_order(ctx, nullptr, "pcl_hess")) return rc;
     KParams p;

@@ -92,9 +92,10 @@ class _PclContext:
         # the exponential constraint: no compact Jacobian, and no Hessian of the Lagrangian (hess_structure / hess raise with the library's
         # message) unless ``exp_hessian`` switches the library's option exp_hess on
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
-        self.exp_hessian = bool(exp_hessian)
-        if self.exp_hessian:
-            self.set_option("exp_hess", 1)
+        self.exp_hessian = False  # (follows the library's option: set_option keeps it and hess_nnz / hess_per current)
+        self.hess_nnz = self.hess_per = 0
+        if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
+            self.set_option("var_exp_hess" if batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess", 1)
         if self.exponential and not self.exp_hessian:
             self.hess_nnz = self.hess_per = 0
         else:
@@ -408,6 +409,13 @@ class _PclContext:
 
     def set_option(self, key, value):
         self._chk(self._L.pcl_set_option(self._h, key.encode(), int(value)))
+        # the option that serves the Hessian of the Lagrangian of this context's exponential constraint: hess_nnz / hess_per follow it
+        if self.exponential and key == ("var_exp_hess" if self.batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess"):
+            self.exp_hessian = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.exp_hessian:
+                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.hess_nnz, self.hess_per = a.value, b.value
 
     def get_option(self, key):
         v = ctypes.c_int64()
@@ -562,9 +570,13 @@ class HipVariationalIntegrator:
     ``pade_order="exp"`` (or -1): the reference's own constraint ``x'_{k+1} = exp(dt_k var_G(..)) x'_k`` instead of a Pade discretisation of
     it -- a context of batch_mode PCL_BATCH_VARIATIONAL_EXP, for the steps whose lifted ``theta`` no Pade order follows.  Residual, Jacobian,
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
-    derivatives: solve with a quasi-Newton Hessian)."""
+    derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``) switches
+    the library's option ``var_exp_hess`` on: the Hessian of the Lagrangian of that constraint is then served too, for generator dimensions up
+    to 44 (nine LDS tiles; beyond that the constructor raises the library's PCL_ESHAPE message).  It is never on by itself."""
 
-    def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10):
+    def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False):
+        if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
+            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -596,7 +608,7 @@ class HipVariationalIntegrator:
             d=sys.levels, m=m, N=traj.N, z_dim=traj.dim, u_off=traj.components[u_name].start, dt_off=traj.components[traj.timestep].start,
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
             batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
-            index_base=index_base, pade_order=pade_order, state_cols=cols,
+            index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian,
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
@@ -661,7 +673,7 @@ def _variational_generators(sys, scales):
 def VariationalUnitaryIntegrator(sys, traj, x_name, x_variations, u_name="u", *, scales=None, **kw):
     """``VariationalUnitaryIntegrator(sys, traj, :U, [:U_var, ...], :u; scales)`` [REF src/control/integrators.jl:247-264]: generator
     ``var_G(I (x) G(u), [I (x) G_var_i / scales[i]])`` on ``vcat(U, U_var_1, ...)``; ``scales`` defaults to ones.  Keyword arguments as for
-    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``)."""
+    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``, ``exp_hessian``)."""
     Gv = _variational_generators(sys, 1.0 if scales is None else scales)
     return HipVariationalIntegrator(sys, traj, x_name, x_variations, u_name, Gv, ket=False, **kw)
 

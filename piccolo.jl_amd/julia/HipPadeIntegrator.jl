@@ -265,11 +265,15 @@ end
 #      The member window does not exist for this mode: the structure is queried whole.
 #      pade_order = :exp (or PCL_ORDER_EXP = -1): batch_mode PCL_BATCH_VARIATIONAL_EXP (= 3), the reference's own constraint
 #      x'_{k+1} = exp(dt_k var_G(..)) x'_k on the stacked state -- residual, Jacobian, objective and rollout; no Hessian of the Lagrangian
-#      (third Frechet derivatives: the structure stays empty, solve with eval_hessian = false).
+#      (third Frechet derivatives: the structure stays empty, solve with eval_hessian = false) unless exp_hessian = true (with
+#      pade_order = :exp only) switches the library's option var_exp_hess on BEFORE the Hessian structure is queried -- generator
+#      dimensions up to 44; never on by itself.  (This keyword's glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
-                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10)
+                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Bool = false)
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
+    (exp_hessian && !expo) &&
+        throw(ArgumentError("HipPadeIntegrator: exp_hessian = true is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order = :exp"))
     m = sys.n_drives
     e(j) = (a = zeros(m); a[j] = 1.0; a)
     zu = zeros(m)
@@ -292,7 +296,8 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     xd = Ref{Int64}(0); nr = Ref{Int64}(0); ncol = Ref{Int64}(0); nnz = Ref{Int64}(0); per = Ref{Int64}(0); hnnz = Ref{Int64}(0)
     check(c, ccall((:pcl_constraint_dim, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), c, xd, nr, ncol))
     check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
-    expo ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
+    (expo && !exp_hessian) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
@@ -301,7 +306,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
     check(c, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, jr, jc))
     hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
-    expo || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
+    (expo && !exp_hessian) || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
     # (B.f is refused for the stacked state, see _f: fcore stays `nothing`)
     return HipPadeIntegrator(core, 1, x, names, u, core.x_dim, core.rows_per, jr, jc, hr, hc, Int(ncol[]), G0, Gj, state_cols, order, nothing)
 end
