@@ -250,7 +250,11 @@ int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *vals);
  * constraint, third Frechet derivatives of exp through an octuple chain per (interval, variation, drive).  Values per interval:
  * (m+1)(m+2)/2 + x_dim'*(m+1), x_dim' the stacked state -- the Pade variational layout without its two X'_{k+1} groups, from pcl_hess_structure
  * as always.  Generator dimensions up to n = 44 (nine LDS tiles); beyond, setting the option is PCL_ESHAPE with the byte counts and the
- * context goes on as before.  Two launches give the same bits.  Get "last_hess_kernel" reads 110 after such a launch. */
+ * context goes on as before.  Two launches give the same bits.  Get "last_hess_kernel" reads 110 after such a launch.
+ * pcl_set_option(ctx, "var_exp_hess_tiles", 1) before "var_exp_hess" serves n = 46 .. 62 too: where nine tiles do not fit, four of them
+ * (Tab, Tac, Tbc, Tabc) live in a device workspace of K v max(m,1) 4 n^2 doubles, allocated then, and "last_hess_kernel" reads 112; where
+ * they fit, nothing changes (110).  2: that plan at every n (the same bits as the LDS plan).  0, the default: as above.  The value is read
+ * when "var_exp_hess" is set to 1; another value while that option is 1 is PCL_EINVAL, and so is a non-zero value on any other context. */
 int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals);
 
 /* device-pointer evaluation (asynchronous on the context's stream; results stay in HBM) ---- */

@@ -37,6 +37,9 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         else
             ctx->var_exp_hess = 0;
     }
+    else if (!strcmp(key, "var_exp_hess_tiles")) {  // ... where the octuple chain's tiles live: 0 nine in LDS | 1 four in the workspace where nine do not fit | 2 always
+        TRY(var_exp_hess_set_tiles(ctx, v));
+    }
 #ifdef PCL_PROFILE
     else if (!strcmp(key, "profile_flags"))  // profiling experiments (results may be WRONG); not present in the shipped library
         ctx->opt_prof = v;
@@ -176,6 +179,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->exp_hess;
     else if (!strcmp(key, "var_exp_hess"))
         *v = ctx->var_exp_hess;
+    else if (!strcmp(key, "var_exp_hess_tiles"))
+        *v = ctx->opt_vexph_tiles;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

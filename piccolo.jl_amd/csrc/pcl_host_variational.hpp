@@ -6,6 +6,7 @@
 #include "pcl_kernel_var_rollout.hpp"
 #include "pcl_kernel_var_exp.hpp"
 #include "pcl_kernel_var_exp_hess.hpp"
+#include "pcl_kernel_var_exp_hess_tiles.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
@@ -432,6 +433,14 @@ static size_t var_exp_hess_lds_bytes(const pcl_ctx *ctx, bool oct, int *g_lds) {
     if (g_lds) *g_lds = g ? 1 : 0;
     return g ? base + tile : base;
 }
+// The same octuple with four tiles in the workspace (option var_exp_hess_tiles; pcl_kernel_var_exp_hess_tiles.hpp): T, Ta, Tb, Tc and the scratch
+// stay resident, G(u_k) takes a sixth tile where that fits.
+static size_t var_exp_hess_ws_lds_bytes(const pcl_ctx *ctx, int *g_lds) {
+    const size_t tile = var_exp_hess_tile_bytes(ctx), base = 5 * tile;
+    const bool g = base + tile <= (size_t)ctx->max_lds;
+    if (g_lds) *g_lds = g ? 1 : 0;
+    return g ? base + tile : base;
+}
 static long long var_exp_hess_part_per(const pcl_ctx *ctx) {
     const long long m = ctx->desc.n_drives;
     return (m + 1) * (m + 2) / 2 + (m + 1) * ctx->var_xdc;
@@ -440,9 +449,14 @@ static long long var_exp_hess_part_per(const pcl_ctx *ctx) {
 static int var_exp_hess_enable(pcl_ctx *ctx) {
     if (!ctx->vexp) return fail(ctx, PCL_EINVAL, "var_exp_hess = 1 needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)");
     const size_t need = var_exp_hess_lds_bytes(ctx, true, nullptr);
-    if (need > (size_t)ctx->max_lds)
-        return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1: the octuple chain of third Frechet derivatives needs %zu B of LDS (> %d) for n=%d: nine n x n tiles of %zu B (a plan with tiles in the workspace is not built)",
+    // the plan: nine LDS tiles, or five and four in the workspace (var_exp_hess_tiles = 2: always; 1: where nine do not fit)
+    const bool ws_plan = ctx->opt_vexph_tiles == 2 || (ctx->opt_vexph_tiles == 1 && need > (size_t)ctx->max_lds);
+    if (!ws_plan && need > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1: the octuple chain of third Frechet derivatives needs %zu B of LDS (> %d) for n=%d: nine n x n tiles of %zu B (option var_exp_hess_tiles = 1 keeps four of them in the workspace)",
                     need, ctx->max_lds, ctx->n, var_exp_hess_tile_bytes(ctx));
+    if (ws_plan && var_exp_hess_ws_lds_bytes(ctx, nullptr) > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1 with var_exp_hess_tiles = %d: the five resident tiles of the octuple chain need %zu B of LDS (> %d) for n=%d: n x n tiles of %zu B",
+                    ctx->opt_vexph_tiles, var_exp_hess_ws_lds_bytes(ctx, nullptr), ctx->max_lds, ctx->n, var_exp_hess_tile_bytes(ctx));
     // the last phase keeps two n x cols products per spent tile, and N_0 .. N_v in three pieces
     if (2 * ctx->cols > ctx->n || ctx->var > 2)
         return fail(ctx, PCL_ESHAPE, "var_exp_hess = 1: %d state columns and %d variations; the kernel's last phase takes cols <= n / 2 = %d and at most 2 variations", ctx->cols, ctx->var, ctx->n / 2);
@@ -458,7 +472,24 @@ static int var_exp_hess_enable(pcl_ctx *ctx) {
             HIP_TRY(ctx, e);
         }
     }
+    if (ws_plan && !ctx->dvexph_tiles) {  // the homes of Tab, Tac, Tbc, Tabc: 4 n^2 doubles per octuple workgroup
+        ON_DEVICE(ctx);
+        const size_t homes = (size_t)ctx->K * ctx->var * std::max(ctx->desc.n_drives, 1) * 4 * (size_t)ctx->n * ctx->n;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dvexph_tiles, homes * sizeof(double)));
+    }
+    ctx->vexph_ws = ws_plan ? 1 : 0;
     ctx->var_exp_hess = 1;
+    return PCL_OK;
+}
+// option var_exp_hess_tiles: read by var_exp_hess_enable, so it takes effect when var_exp_hess is next set to 1; another value while that
+// option is on is refused
+static int var_exp_hess_set_tiles(pcl_ctx *ctx, int64_t v) {
+    if (v < 0 || v > 2) return fail(ctx, PCL_EINVAL, "var_exp_hess_tiles must be 0, 1 or 2");
+    if (v && !ctx->vexp)
+        return fail(ctx, PCL_EINVAL, "var_exp_hess_tiles = %d needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)", (int)v);
+    if (ctx->var_exp_hess && v != ctx->opt_vexph_tiles)
+        return fail(ctx, PCL_EINVAL, "var_exp_hess_tiles cannot change while var_exp_hess = 1 (it is %d): set var_exp_hess = 0 first", ctx->opt_vexph_tiles);
+    ctx->opt_vexph_tiles = (int)v;
     return PCL_OK;
 }
 static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
@@ -470,7 +501,10 @@ static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, 
     VarExpHessParams p;
     memset(&p, 0, sizeof p);
     int g_quad = 0, g_oct = 0;
-    const size_t lds_quad = var_exp_hess_lds_bytes(ctx, false, &g_quad), lds_oct = var_exp_hess_lds_bytes(ctx, true, &g_oct);
+    const bool ws_plan = ctx->vexph_ws != 0;
+    if (ws_plan && !ctx->dvexph_tiles) return fail(ctx, PCL_EINVAL, "pcl_hess: the workspace of option var_exp_hess_tiles is missing");
+    const size_t lds_quad = var_exp_hess_lds_bytes(ctx, false, &g_quad);
+    const size_t lds_oct = ws_plan ? var_exp_hess_ws_lds_bytes(ctx, &g_oct) : var_exp_hess_lds_bytes(ctx, true, &g_oct);
     const long long grid = (long long)ctx->K * v * ml;
     p.pper = var_exp_hess_part_per(ctx);
     const long long fin = ((long long)ctx->K * p.pper + 255) / 256;
@@ -500,15 +534,17 @@ static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, 
     void *args[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel((const void *)pcl_var_exp_hess_prep_kernel, dim3((unsigned)ctx->K), dim3(256), args, lds_prep, ctx->stream));
     const unsigned threads = n > 32 ? 512 : 256;  // (as the sibling kernels: a pair of output tiles per wave)
-    const void *fq = (const void *)pcl_var_exp_hess_kernel<false>, *fo = (const void *)pcl_var_exp_hess_kernel<true>;
+    const void *fq = (const void *)pcl_var_exp_hess_kernel<false>;
+    const void *fo = ws_plan ? (const void *)pcl_var_exp_hess_tiles_kernel : (const void *)pcl_var_exp_hess_kernel<true>;
     if (int rc = var_set_lds(ctx, fq, lds_quad)) return rc;
     if (int rc = var_set_lds(ctx, fo, lds_oct)) return rc;
     p.g_lds = g_quad;
     HIP_TRY(ctx, hipLaunchKernel(fq, dim3((unsigned)(ctx->K * ml)), dim3(threads), args, lds_quad, ctx->stream));
     p.g_lds = g_oct;
-    HIP_TRY(ctx, hipLaunchKernel(fo, dim3((unsigned)grid), dim3(threads), args, lds_oct, ctx->stream));
+    void *args_ws[] = {&p, &ctx->dvexph_tiles};  // (the plan with tiles in the workspace: the homes as a second argument)
+    HIP_TRY(ctx, hipLaunchKernel(fo, dim3((unsigned)grid), dim3(threads), ws_plan ? args_ws : args, lds_oct, ctx->stream));
     HIP_TRY(ctx, hipLaunchKernel((const void *)pcl_var_exp_hess_finish_kernel, dim3((unsigned)fin), dim3(256), args, 0, ctx->stream));
-    ctx->last_hess_kernel = 110;
+    ctx->last_hess_kernel = ws_plan ? 112 : 110;
     return PCL_OK;
 }
 

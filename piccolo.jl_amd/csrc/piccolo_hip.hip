@@ -11,6 +11,7 @@
 //   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
 //   pcl_kernel_exp_hess.hpp    ... its Hessian of the Lagrangian (option exp_hess): second Frechet derivatives, one chain per drive
 //   pcl_kernel_var_exp_hess.hpp ... the same of a variational context (option var_exp_hess): third Frechet derivatives, an octuple chain per (variation, drive)
+//   pcl_kernel_var_exp_hess_tiles.hpp ... its octuple chain with four tiles in a device workspace (option var_exp_hess_tiles): generator dimensions 46 .. 62
 //   pcl_kernel_var_exp.hpp     the variational integrators on the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): residual and Jacobian
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
@@ -71,6 +72,9 @@ struct pcl_ctx {
     int vexp = 0;           // ... PCL_BATCH_VARIATIONAL_EXP: the exponential constraint on the lifted generator (pcl_kernel_var_exp.hpp; its workspace is dexph)
     int var_exp_hess = 0;   // ... ... option var_exp_hess: its Hessian of the Lagrangian is served (pcl_kernel_var_exp_hess.hpp)
     double *dvexph = nullptr, *dvexph_part = nullptr;  // ... ... that launch's workspace [G(u_k) | norm | W_0 | W_i] and partial sums, per interval
+    int opt_vexph_tiles = 0;  // ... ... option var_exp_hess_tiles: 0 nine LDS tiles | 1 four of them in the workspace where nine do not fit | 2 always
+    int vexph_ws = 0;         // ... ... the plan in force since var_exp_hess was last set to 1 (pcl_kernel_var_exp_hess_tiles.hpp)
+    double *dvexph_tiles = nullptr;  // ... ... the homes of Tab, Tac, Tbc, Tabc per octuple workgroup (allocated when that plan is first chosen)
     long long var_xdc = 0;  // ... x_dim of one component
     int var_nl = 0;         // ... dimension of the lifted generator (the order policy's norms)
     double *dvar_tab = nullptr;  // ... [G_drift | G_l | Gv_i | the same transposed], n x n column-major each
@@ -668,7 +672,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);

@@ -51,14 +51,27 @@ def _ptr(a):
     raise TypeError("unsupported buffer type %r" % type(a))
 
 
+def _exp_hessian_value(exp_hessian):
+    """The keyword ``exp_hessian``: ``False`` | ``True`` | ``"workspace"`` (anything else: ``ValueError``, before any device call)."""
+    if isinstance(exp_hessian, (bool, np.bool_)) or (isinstance(exp_hessian, (int, np.integer)) and exp_hessian in (0, 1)):
+        return bool(exp_hessian)
+    if isinstance(exp_hessian, str) and exp_hessian == "workspace":
+        return exp_hessian
+    raise ValueError("exp_hessian must be False, True or \"workspace\" (got %r)" % (exp_hessian,))
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False):  # fmt: skip
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
+        exp_hessian = _exp_hessian_value(exp_hessian)
         if exp_hessian and pade_order != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
+        if exp_hessian == "workspace" and batch_mode != PCL_BATCH_VARIATIONAL_EXP:
+            raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint (option var_exp_hess_tiles): "
+                             "it needs a variational context with pade_order=\"exp\"")
         self._L = _lib.load()
         self._h = None
         n = d if state_cols == _lib.PCL_STATE_VECTOR else 2 * d  # PCL_STATE_VECTOR: general d x d generator, one column
@@ -94,6 +107,8 @@ class _PclContext:
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         self.exp_hessian = False  # (follows the library's option: set_option keeps it and hess_nnz / hess_per current)
         self.hess_nnz = self.hess_per = 0
+        if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
+            self.set_option("var_exp_hess_tiles", 1)
         if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
             self.set_option("var_exp_hess" if batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess", 1)
         if self.exponential and not self.exp_hessian:
@@ -481,6 +496,9 @@ class HipPadeIntegrator:
         and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own.
         ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served too
         (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62."""
+        exp_hessian = _exp_hessian_value(exp_hessian)
+        if exp_hessian == "workspace":
+            raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint: a plain integrator takes False or True")
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         x_names = [x_name] if isinstance(x_name, str) else list(x_name)
@@ -572,9 +590,12 @@ class HipVariationalIntegrator:
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
     derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``) switches
     the library's option ``var_exp_hess`` on: the Hessian of the Lagrangian of that constraint is then served too, for generator dimensions up
-    to 44 (nine LDS tiles; beyond that the constructor raises the library's PCL_ESHAPE message).  It is never on by itself."""
+    to 44 (nine LDS tiles; beyond that the constructor raises the library's PCL_ESHAPE message).  ``exp_hessian="workspace"`` sets the option
+    ``var_exp_hess_tiles`` = 1 first: where nine tiles exceed the LDS (generator dimensions 46 .. 62, config 3 among them) four of them live in
+    a device workspace, elsewhere nothing changes.  Any other value is a ``ValueError``.  It is never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False):
+        exp_hessian = _exp_hessian_value(exp_hessian)
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
@@ -673,7 +694,7 @@ def _variational_generators(sys, scales):
 def VariationalUnitaryIntegrator(sys, traj, x_name, x_variations, u_name="u", *, scales=None, **kw):
     """``VariationalUnitaryIntegrator(sys, traj, :U, [:U_var, ...], :u; scales)`` [REF src/control/integrators.jl:247-264]: generator
     ``var_G(I (x) G(u), [I (x) G_var_i / scales[i]])`` on ``vcat(U, U_var_1, ...)``; ``scales`` defaults to ones.  Keyword arguments as for
-    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``, ``exp_hessian``)."""
+    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``, ``exp_hessian``: ``False`` | ``True`` | ``"workspace"``)."""
     Gv = _variational_generators(sys, 1.0 if scales is None else scales)
     return HipVariationalIntegrator(sys, traj, x_name, x_variations, u_name, Gv, ket=False, **kw)
 

@@ -267,11 +267,17 @@ end
 #      x'_{k+1} = exp(dt_k var_G(..)) x'_k on the stacked state -- residual, Jacobian, objective and rollout; no Hessian of the Lagrangian
 #      (third Frechet derivatives: the structure stays empty, solve with eval_hessian = false) unless exp_hessian = true (with
 #      pade_order = :exp only) switches the library's option var_exp_hess on BEFORE the Hessian structure is queried -- generator
-#      dimensions up to 44; never on by itself.  (This keyword's glue has not been executed: no Julia on the development machines.)
+#      dimensions up to 44; never on by itself.  exp_hessian = :workspace sets the option var_exp_hess_tiles = 1 first: where nine LDS tiles do
+#      not fit (generator dimensions 46 .. 62, config 3 among them) four of them live in a device workspace.  Any other value: ArgumentError.
+#      (This keyword's glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
-                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Bool = false)
+                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false)
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
+    (exp_hessian isa Symbol && exp_hessian != :workspace) &&
+        throw(ArgumentError("HipPadeIntegrator: exp_hessian must be false, true or :workspace (got :$(exp_hessian))"))
+    workspace = exp_hessian === :workspace
+    exp_hessian = exp_hessian !== false
     (exp_hessian && !expo) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian = true is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order = :exp"))
     m = sys.n_drives
@@ -296,6 +302,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     xd = Ref{Int64}(0); nr = Ref{Int64}(0); ncol = Ref{Int64}(0); nnz = Ref{Int64}(0); per = Ref{Int64}(0); hnnz = Ref{Int64}(0)
     check(c, ccall((:pcl_constraint_dim, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), c, xd, nr, ncol))
     check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    workspace && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess_tiles", 1))
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
     (expo && !exp_hessian) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
