@@ -97,7 +97,8 @@ typedef enum pcl_status {
  * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, pcl_rollout[_dev] and the whole
  * objective family -- the last three with the bits a Pade context of the same system gives.  PCL_ENOTIMPL: pcl_hess[_dev], pcl_hess_nnz,
  * pcl_hess_structure[_i64] (the (u_i, u_j) block of the Hessian of the Lagrangian needs second Frechet derivatives: opt in below, or solve
- * with a quasi-Newton Hessian, the reference's eval_hessian = false), the compact Jacobian trio and the merit / reduce entry points.
+ * with a quasi-Newton Hessian, the reference's eval_hessian = false), the compact Jacobian trio and the merit / reduce entry points (pcl_merit_grad_len,
+ * pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev) -- both groups: opt in below.
  * pcl_set_order_policy and pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  get_option "pade_order" reads -1,
  * "last_kernel" 100 (residual + Jacobian) or 101 (residual only).
  *
@@ -110,7 +111,25 @@ typedef enum pcl_status {
  *     seg 0  (u_i, u_j), j <= i : -<M, L2(hG; hG_i, hG_j) X_k>        seg 3  for l<m, r<x_dim : (u_l, X_k[r])   -(L_l' M)[r]
  *     seg 1  (dt, u_j)          : -<M, (G_j E + G L_j) X_k>           seg 4  for r<x_dim      : (dt,  X_k[r])   -((G E)' M)[r]
  *     seg 2  (dt, dt)           : -<M, G G E X_k>
- * get_option "last_hess_kernel" reads 100 after such a launch.  The other refusals of the mode do not depend on the option. */
+ * get_option "last_hess_kernel" reads 100 after such a launch.  The other refusals of the mode do not depend on the option.
+ *
+ * The compact Jacobian, the host expansion and the reduce payload, by option: pcl_set_option(ctx, "exp_full", 1) on such a context (0, the default:
+ * the refusals above, in the same words, and host-pointer calls that deliver full values; 1 on any other context -- Pade, variational of either
+ * kind --: PCL_EINVAL; reading works everywhere; independent of "exp_hess") serves the seven entry points named above:
+ *   - the compact trio: per (member b, interval k) the unique values are  [ -E (n*n) | tail (x_dim*(m+1), exactly the full layout's tail) ],
+ *     n*n + x_dim*(m+1) doubles (pcl_jac_compact_nnz; the ones of seg 1 are constants and no part of it).  pcl_eval_jac_compact_dev runs the
+ *     recurrence of the full launch and stores one -E per interval ("last_kernel" 102); pcl_jac_expand_dev writes cols copies of -E, x_dim ones and
+ *     the tail: bit for bit what pcl_eval_jac_dev writes, and delta has its bits too.  pcl_set_member_window applies as on a Pade context.
+ *   - pcl_eval_jac / pcl_jac with more than one state column take the compact path unless "host_path" = 1 (compact launch, chunked copies into
+ *     pinned staging, the host's threads replicate): the caller's array receives the bits of the full path.
+ *   - pcl_merit_grad_len / pcl_merit_grad_dev as on a Pade context (the tails start behind cols*n*n + x_dim values); pcl_eval_jac_merit_dev forms the
+ *     payload's partial sums inside the Jacobian launch, reduced per workgroup in a fixed order ("last_merit_fused" 1; delta and vals exactly as by
+ *     pcl_eval_jac_dev); pcl_eval_jac_merit_objective_dev runs its two-call fallback.  All of every member, as documented at the member window.
+ *   - pcl_eval_jac_merit_dev with vals_dev == NULL (PCL_EINVAL everywhere else): delta and the payload WITHOUT the Jacobian.  With A = h G(u_k),
+ *     W = Lam X_k' and V = L(A'; W):  <Lam, L(A; h G_l) X_k> = h <V, G_l>,  <Lam, G E X_k> = <V, G0> + sum_l u_l <V, G_l>  -- one pair chain per
+ *     (member, interval) instead of one per drive, behind the residual-only launch and a preparation launch; a workspace of
+ *     batch*K*(2 n*n + 2) doubles is allocated on first use (shared with "exp_hess"), freed by pcl_destroy.  "last_kernel" 103, "last_merit_fused" 0.
+ *   Every payload launch is deterministic: two launches give the same bits. */
 #define PCL_ORDER_EXP (-1)
 
 #define PCL_MAX_D 32 /* n = 2d <= 64: G(u_k), G^2 and the column tiles stay LDS-resident */
@@ -278,7 +297,9 @@ int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count);
 
 /* Compact Jacobian: the d diagonal copies of I_d (x) B^{+-} are identical, so per (b,k) only
  * [-B^+ (n*n) | B^- (n*n) | d/du (m*x_dim) | d/ddt (x_dim)] = 2 n^2 + x_dim (m+1) doubles are unique.
- * pcl_eval_jac_compact_dev writes those; pcl_jac_expand_dev replicates them into the full triplet order. */
+ * pcl_eval_jac_compact_dev writes those; pcl_jac_expand_dev replicates them into the full triplet order.
+ * A context of the exponential constraint with option "exp_full" = 1 (see PCL_ORDER_EXP): [-E (n*n) | tail (x_dim*(m+1))] = n^2 + x_dim (m+1)
+ * doubles per (b,k); the expansion writes cols copies of -E, the x_dim ones of d delta / d X_{k+1}, then the tail. */
 int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *nnz_per_interval);
 int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z_dev, double *delta_dev, double *compact_dev);
 int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact_dev, double *vals_dev);
@@ -361,7 +382,8 @@ int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, do
  * summed over ranks with pcl_reduce_sum_dev; TRAJ mode: `sets` = batch sets (nothing is shared between seeds). */
 int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets);
 int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta_dev, const double *lam_dev, const double *vals_dev, double *out_dev);
-/* pcl_eval_jac_dev + pcl_merit_grad_dev in one pass: the fused kernel forms the payload's dot products per state column while the
+/* (vals_dev == NULL: PCL_EINVAL, except on a context of the exponential constraint with option "exp_full" = 1 -- the payload without the Jacobian.)
+ * pcl_eval_jac_dev + pcl_merit_grad_dev in one pass: the fused kernel forms the payload's dot products per state column while the
  * column's vectors are still in LDS (the 1.7 % of the Jacobian values that pcl_merit_grad_dev reads back from HBM are never
  * re-read); delta_dev and vals_dev are written exactly as by pcl_eval_jac_dev.  Launches that do not take fused kernel 3 (other
  * shapes, Pade orders other than 4, a member window) run the two calls one after the other: same outputs, same layout.
@@ -409,6 +431,8 @@ int pcl_comm_destroy(pcl_ctx *ctx);
  *   "host_threads"  threads that expand the compact values into the caller's array in the host-pointer entry points (0 = min(cores / 2, 32);
  *                   -1 = a sweep over the context's first twelve calls), "host_path" (0 auto | 1 full values over PCIe | 2 compact + host expansion)
  *   "v4_ticket"     launches of several trajectories: -1 auto | 0 static split | 1 groups of workgroups + slice tickets
+ *   "exp_full"      contexts of the exponential constraint only (1 on any other context: PCL_EINVAL): 1 serves the compact Jacobian trio, the compact
+ *                   host-pointer path and the merit / reduce entry points (see PCL_ORDER_EXP); 0 (default) refuses them
  *   "var_full"      variational contexts only (1 on any other context: PCL_EINVAL): 1 serves the objective entry points and the rollout
  *                   (see PCL_BATCH_VARIATIONAL); 0 (default) refuses them and drops goal, weights and regularisers
  * and reads: "pade_order" (the order in use), "last_kernel" / "last_hess_kernel" (which kernel family ran), "jit_compiles", "jit_cache_hits",

@@ -141,6 +141,21 @@ static inline void expand_interval(double *__restrict__ full, const double *__re
     }
 }
 
+// The same for a context of the exponential constraint (option exp_full): compact [-E (nn) | tail] -> full [-E x cols | ones (xd) | tail].
+// half 0: the first (cols + 1) / 2 copies of -E; half 1: the other copies, the ones and the tail.
+static inline void expand_interval_exp(double *__restrict__ full, const double *__restrict__ compact, int cols, long long nn, long long xd, long long tail, int half,
+                                       stream_copy_fn copy) {
+    const int mid = (cols + 1) / 2;
+    if (half == 0) {
+        for (int c = 0; c < mid; ++c) copy(full + (long long)c * nn, compact, (size_t)nn);
+    } else {
+        for (int c = mid; c < cols; ++c) copy(full + (long long)c * nn, compact, (size_t)nn);
+        double *ones = full + (long long)cols * nn;
+        for (long long e = 0; e < xd; ++e) ones[e] = 1.0;
+        copy(ones + xd, compact + nn, (size_t)tail);
+    }
+}
+
 // CPUs the cgroup grants this process (cpu.max = "quota period", cgroup v2; cfs_quota_us / cfs_period_us, v1); 0: no quota.  A container may see
 // 256 hardware threads and be allowed 16 CPUs' worth of time: a team above the quota wins single calls and is throttled over a run.
 static inline double cgroup_quota_cpus() {

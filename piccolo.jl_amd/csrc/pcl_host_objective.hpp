@@ -355,32 +355,86 @@ extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *va
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PCL_OK;
 }
+// the payload from the partial sums in ctx->dphik: the members in order with their weights, then phi over the intervals in order
+static int merit_sum(pcl_ctx *ctx, double *out) {
+    const pcl_desc &D = ctx->desc;
+    const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
+    const int sets = traj ? D.batch : 1;
+    double *phik = ctx->dphik + (size_t)D.batch * ctx->K * (D.n_drives + 2);
+    hipLaunchKernelGGL(pcl_merit_sum_kernel, dim3((unsigned)sets), dim3(1024), 0, ctx->stream, (const double *)ctx->dphik,
+                       (const double *)ctx->dweights, out, phik, D.batch, ctx->K, D.n_drives, traj ? 1 : 0);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCL_OK;
+}
+// The payload of an exponential context without its Jacobian (option exp_full; pcl_kernel_exp_merit.hpp): the residual-only launch, the
+// Hessian's prep kernel with Lam = lam (NULL: the residual just written) for [G(u_k) | Lam X_k' | |G|_1], one adjoint pair chain per
+// (member, interval), the sum kernel.  Every member, whatever the member window says.
+static int launch_exp_merit(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *out) {
+    ON_DEVICE(ctx);
+    if (int rc = check_device_error(ctx, "pcl_eval_jac_merit_dev")) return rc;
+    const pcl_desc &D = ctx->desc;
+    const int wf = ctx->win_first, wc = ctx->win_count;
+    ctx->win_first = 0, ctx->win_count = D.batch;
+    KParams p;
+    fill_params(ctx, p);
+    ctx->win_first = wf, ctx->win_count = wc;
+    p.Z = Z;
+    p.delta = delta;
+    const size_t tile = (size_t)p.LD * p.n, lds = (4 * tile + 16) * sizeof(double);
+    const size_t lds_prep = (tile + 32 + 64 + 2 * (size_t)p.n * p.cols) * sizeof(double);  // G(u_k), the drives, the column sums, X_k and Lam
+    if (lds > (size_t)ctx->max_lds || lds_prep > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "pcl_eval_jac_merit_dev: the adjoint chain kernel needs %zu B of LDS (> %d) for n=%d: four n x n tiles of %zu B", std::max(lds, lds_prep),
+                    ctx->max_lds, p.n, tile * sizeof(double));
+    const long long items = (long long)p.batch * p.K;
+    if (items > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    TRY(merit_scratch(ctx));
+    const long long cap = items * (2LL * p.n * p.n + 2);  // (the workspace of the Hessian launches: the same layout, the same stream)
+    if (ctx->exph_cap < cap) {
+        if (ctx->dexph) (void)hipFree(ctx->dexph);
+        ctx->dexph = nullptr, ctx->exph_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dexph, (size_t)cap * sizeof(double)));
+        ctx->exph_cap = cap;
+    }
+    TRY(launch_exp(ctx, p, false));
+    p.mu = lam ? lam : delta;
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_exp_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+    hipLaunchKernelGGL(pcl_exp_hess_prep_kernel, dim3((unsigned)items), dim3(256), lds_prep, ctx->stream, p, ctx->dexph);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_exp_merit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned threads = p.n > 32 ? 512 : 256;  // (as the Jacobian kernel: a pair of output tiles per wave)
+    hipLaunchKernelGGL(pcl_exp_merit_kernel, dim3((unsigned)items), dim3(threads), lds, ctx->stream, p, (const double *)ctx->dGjd, (const double *)ctx->dexph, lam,
+                       (const double *)delta, ctx->dphik);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_kernel = 103;  // the adjoint payload launch
+    return merit_sum(ctx, out);
+}
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
     VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
-    EXP_NOTIMPL(ctx, "pcl_merit_grad_dev");
+    EXP_FULL_GATE(ctx, "pcl_merit_grad_dev");
     if (!ctx) return PCL_EINVAL;
     if (!delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_merit_grad_dev: NULL pointer");
     ON_DEVICE(ctx);
     const pcl_desc &D = ctx->desc;
-    const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
-    const int sets = traj ? D.batch : 1;
     const int m = D.n_drives;
-    if (!ctx->dphik) HIP_TRY(ctx, hipMalloc((void **)&ctx->dphik, ((size_t)D.batch * ctx->K * (m + 2) + (size_t)sets * ctx->K) * sizeof(double)));
-    double *part = ctx->dphik, *phik = ctx->dphik + (size_t)D.batch * ctx->K * (m + 2);
-    hipLaunchKernelGGL(pcl_merit_part_kernel, dim3((unsigned)ctx->K, (unsigned)D.batch), dim3(512), 0, ctx->stream, delta, lam, vals, part,
-                       ctx->K, ctx->cols, ctx->n, m, jac_per_full(ctx), 2LL * ctx->cols * ctx->n * ctx->n);
+    TRY(merit_scratch(ctx));
+    // the tails start behind the blocks: 2 cols n^2 of a Pade context, cols n^2 and the x_dim ones of an exponential one
+    const long long tail_off = ctx->exp ? (long long)ctx->cols * ctx->n * ctx->n + ctx->x_dim : 2LL * ctx->cols * ctx->n * ctx->n;
+    hipLaunchKernelGGL(pcl_merit_part_kernel, dim3((unsigned)ctx->K, (unsigned)D.batch), dim3(512), 0, ctx->stream, delta, lam, vals, ctx->dphik,
+                       ctx->K, ctx->cols, ctx->n, m, jac_per_full(ctx), tail_off);
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(pcl_merit_sum_kernel, dim3((unsigned)sets), dim3(1024), 0, ctx->stream, (const double *)part,
-                       (const double *)ctx->dweights, out, phik, D.batch, ctx->K, m, traj ? 1 : 0);
-    HIP_TRY(ctx, hipGetLastError());
-    return PCL_OK;
+    return merit_sum(ctx, out);
 }
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
-    EXP_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
+    if (ctx && ctx->exp && !ctx->exp_full && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
+    EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_dev");
     if (!ctx) return PCL_EINVAL;
+    if (Z && delta && out && !vals && ctx->exp_full) {  // the payload alone: no Jacobian value is formed
+        ctx->merit_fused = 0;
+        return launch_exp_merit(ctx, Z, lam, delta, out);
+    }
     if (!Z || !delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");
     ctx->merit_want = 1;
     ctx->merit_fused = 0;
@@ -391,6 +445,7 @@ extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const doubl
     if (rc != PCL_OK) return rc;
     if (!ctx->merit_fused) return pcl_merit_grad_dev(ctx, delta, lam, vals, out);  // other kernels / member windows: the separate payload kernels
     ON_DEVICE(ctx);
+    if (ctx->exp) return merit_sum(ctx, out);  // (the exponential kernel left the sums per (member, interval): nothing to add over columns)
     const pcl_desc &D = ctx->desc;
     const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
     const int sets = traj ? D.batch : 1;
@@ -601,14 +656,14 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
-    EXP_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
+    EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out || !value) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: no goal set");
     TRY(objective_unitary_only(ctx, "pcl_eval_jac_merit_objective_dev"));
     int skip_lo = 0, skip_hi = 0;
     ctx->last_step_launches = 4;
-    if (!tail_applies(ctx, grad, skip_lo, skip_hi)) {
+    if (ctx->exp || !tail_applies(ctx, grad, skip_lo, skip_hi)) {  // (an exponential context: always the two calls)
         TRY(pcl_objective_dev(ctx, Z, Q, value, grad));
         ctx->last_step_launches = 2 + ctx->last_objective_launches;
         return pcl_eval_jac_merit_dev(ctx, Z, lam, delta, vals, out);
@@ -631,7 +686,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
     VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
-    EXP_NOTIMPL(ctx, "pcl_merit_grad_len");
+    EXP_FULL_GATE(ctx, "pcl_merit_grad_len");
     if (!ctx) return PCL_EINVAL;
     if (len) *len = 1 + (int64_t)ctx->K * ctx->desc.n_drives + ctx->K;
     if (sets) *sets = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;

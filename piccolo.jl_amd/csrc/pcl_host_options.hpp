@@ -30,6 +30,11 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v) TRY(exp_hess_fits(ctx, "exp_hess = 1"));
         ctx->exp_hess = (int)v;
     }
+    else if (!strcmp(key, "exp_full")) {  // exponential contexts: serve the compact Jacobian trio, the host expansion and the merit / reduce payload (0: refuse them, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "exp_full must be 0 or 1");
+        if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_full = 1 needs a plain context of the exponential constraint (PCL_ORDER_EXP, not a variational one)");
+        ctx->exp_full = (int)v;
+    }
     else if (!strcmp(key, "var_exp_hess")) {  // variational contexts of the exponential constraint: serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_exp_hess must be 0 or 1");
         if (v)
@@ -177,6 +182,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->var_full;
     else if (!strcmp(key, "exp_hess"))
         *v = ctx->exp_hess;
+    else if (!strcmp(key, "exp_full"))
+        *v = ctx->exp_full;
     else if (!strcmp(key, "var_exp_hess"))
         *v = ctx->var_exp_hess;
     else if (!strcmp(key, "var_exp_hess_tiles"))

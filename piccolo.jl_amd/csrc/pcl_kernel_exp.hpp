@@ -21,14 +21,27 @@
 //                          m = 0: no Frechet pair, the T recurrence alone.
 //   pcl_exp_kernel<false>  residual only: one workgroup per (member, interval), E alone -- the same T recurrence and the same product E X_k,
 //                          hence the delta bits of the fused launch.
+//   MODE (option exp_full; the default 0 is the kernel above, expression for expression -- every variant computes E, L_l and the products by
+//   the same sequence, so delta and every value carry the bits of MODE 0):
+//     PCL_EXP_COMPACT      the compact Jacobian: per interval [-E (n n) | tail], one copy of -E (stored by workgroup 0) and no ones
+//                          (pcl_eval_jac_compact_dev; pcl_exp_expand_kernel replicates).
+//     PCL_EXP_MERIT        the full values and, while the operands are in LDS, the reduce payload's partial sums (pcl_eval_jac_merit_dev):
+//                          workgroup l leaves <lam, -L_l X_k> in part[bk (m + 2) + l], workgroup 0 also <lam, -G E X_k> in slot m and
+//                          <lam, delta> in slot m + 1 (lam == NULL: lam = delta, slot m + 1 holds |delta|^2 / 2; a workgroup l > 0 then forms
+//                          E X_k for itself, one more small product).  Each sum is reduced over the workgroup in a fixed order and written
+//                          by a plain store: no atomic, no wait between workgroups; pcl_merit_sum_kernel finishes.
 // Four rotating n x n tiles (G, T, Tv, one scratch; G's tile is the second scratch of the squarings) and the n x cols tile of X_k: 149 KB at
 // n = 64 with 32 columns.  G_l has a fifth tile where that fits the LDS and is read from L2 by the product where not.  The products L_l X_k,
 // E X_k and G (E X_k) land in spent tiles.  Every product goes through gemm_lds on the f64 matrix cores.
 #pragma once
 
-template <bool JAC>
+#define PCL_EXP_COMPACT 1
+#define PCL_EXP_MERIT 2
+
+template <bool JAC, int MODE = 0>
 __global__ __launch_bounds__(512) void pcl_exp_kernel(const KParams p, const double *__restrict__ Gjd, const int gl_lds) {
     extern __shared__ double lds[];
+    constexpr bool COMPACT = JAC && (MODE & PCL_EXP_COMPACT), MERIT = JAC && (MODE & PCL_EXP_MERIT);
     const int n = p.n, LD = p.LD, nn = n * n, cols = p.cols;
     const int tid = threadIdx.x, nth = blockDim.x;
     const int ml = JAC ? max(p.m, 1) : 1;
@@ -121,12 +134,25 @@ __global__ __launch_bounds__(512) void pcl_exp_kernel(const KParams p, const dou
     for (int e = tid; e < ne; e += nth) XK[(e % n) + LD * (e / n)] = zk[xo + e];
     __syncthreads();
     double *jv = JAC ? p.jac + bk * p.jac_per : nullptr;
-    const long long seg1 = (long long)cols * nn, tail0 = seg1 + ne;
+    const int ncopy = COMPACT ? 1 : cols;  // copies of -E in the interval's block
+    const long long seg1 = (long long)ncopy * nn, tail0 = seg1 + (COMPACT ? 0 : ne);
     const int tw = (p.m + 1) * n;  // tail doubles per state column
+    const double *lam = MERIT && p.mlam ? p.mlam + bk * ne : nullptr;
+    double *part = MERIT ? p.mpart + bk * (p.m + 2) : nullptr;
     if (fre) {
         gemm_lds<true, false>(X, LD, XK, LD, S, LD, n, cols, n);  // L_l X_k
+        if (MERIT && !lam) gemm_lds<true, false>(T, LD, XK, LD, A, LD, n, cols, n);  // lam = delta: E X_k (G's tile; workgroup 0 builds G again)
         __syncthreads();
         for (int e = tid; e < ne; e += nth) jv[tail0 + (long long)(e / n) * tw + l * n + (e % n)] = -S[(e % n) + LD * (e / n)];
+        if (MERIT) {
+            double v = 0.0;
+            for (int e = tid; e < ne; e += nth) {
+                const int idx = (e % n) + LD * (e / n);
+                v = fma(lam ? lam[e] : zk[p.z_dim + xo + e] - A[idx], -S[idx], v);
+            }
+            v = exph_block_sum(v, red);
+            if (tid == 0) part[l] = v;
+        }
         __syncthreads();
     }
     if (l == 0) {
@@ -137,7 +163,7 @@ __global__ __launch_bounds__(512) void pcl_exp_kernel(const KParams p, const dou
             for (int e = tid; e < ne; e += nth) dl[e] = zk[p.z_dim + xo + e] - S[(e % n) + LD * (e / n)];
         }
         if (JAC) {
-            if (fre && sq > 0) {  // the squarings of the pair went through G's tile
+            if (fre && (sq > 0 || (MERIT && !lam))) {  // the squarings of the pair (or the payload's E X_k) went through G's tile
                 build_G(p, G0, zk, A, us);
                 __syncthreads();
             }
@@ -145,14 +171,29 @@ __global__ __launch_bounds__(512) void pcl_exp_kernel(const KParams p, const dou
             __syncthreads();
             for (int e = tid; e < ne; e += nth) {
                 jv[tail0 + (long long)(e / n) * tw + p.m * n + (e % n)] = -X[(e % n) + LD * (e / n)];
-                jv[seg1 + e] = 1.0;
+                if (!COMPACT) jv[seg1 + e] = 1.0;
+            }
+            if (MERIT) {  // <lam, -G E X_k> and <lam, delta>; S = E X_k still
+                double vh = 0.0, vp = 0.0;
+                for (int e = tid; e < ne; e += nth) {
+                    const int idx = (e % n) + LD * (e / n);
+                    const double dl = zk[p.z_dim + xo + e] - S[idx], lm = lam ? lam[e] : dl;
+                    vh = fma(lm, -X[idx], vh);
+                    vp = fma(lm, dl, vp);
+                }
+                vh = exph_block_sum(vh, red);
+                vp = exph_block_sum(vp, red);
+                if (tid == 0) {
+                    part[p.m] = vh;
+                    part[p.m + 1] = lam ? vp : 0.5 * vp;
+                }
             }
         }
     }
     if (JAC) {  // the copies of -E with c = l (mod ml)
         if (!(n & 1) && !((unsigned long long)jv & 15ull)) {
             const int half = nn >> 1;
-            for (int c = l; c < cols; c += ml) {
+            for (int c = l; c < ncopy; c += ml) {
                 double *dst = jv + (long long)c * nn;
                 for (int e2 = tid; e2 < half; e2 += nth) {
                     const int e = 2 * e2, idx = (e % n) + LD * (e / n);
@@ -161,7 +202,7 @@ __global__ __launch_bounds__(512) void pcl_exp_kernel(const KParams p, const dou
                 }
             }
         } else {
-            for (int c = l; c < cols; c += ml) {
+            for (int c = l; c < ncopy; c += ml) {
                 double *dst = jv + (long long)c * nn;
                 for (int e = tid; e < nn; e += nth) dst[e] = -T[(e % n) + LD * (e / n)];
             }

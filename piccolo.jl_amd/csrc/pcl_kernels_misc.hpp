@@ -51,6 +51,60 @@ __global__ __launch_bounds__(256) void pcl_expand_kernel(const double *__restric
     }
 }
 
+// The same for a context of the exponential constraint (option exp_full): compact [-E (n n) | tail] -> full [-E x cols | ones (x_dim) | tail].
+//   per interval: S block workgroups (a slice of cpi state columns each: the tile is read once, then only stores) and T tail workgroups
+//   (4096 doubles each; the first also writes the ones).  16-byte accesses where n is even and both arrays are 16-byte aligned (every
+//   block then starts aligned); scalar otherwise (PCL_STATE_VECTOR with an odd n).  Copies only: the bits of the compact values.
+__global__ __launch_bounds__(256) void pcl_exp_expand_kernel(const double *__restrict__ compact, double *__restrict__ full, int cols, int n, int m,
+                                                             long long n_bk, int cpi) {
+    const long long nn = (long long)n * n, xd = (long long)n * cols, tail = xd * (m + 1);
+    const long long cper = nn + tail, fper = cols * nn + xd + tail;
+    const int S = (cols + cpi - 1) / cpi, T = (int)((tail + 4095) / 4096);
+    const int per_bk = S + T;
+    const long long bk = blockIdx.x / per_bk;
+    const int r = (int)(blockIdx.x - bk * per_bk);
+    if (bk >= n_bk) return;
+    const double *src = compact + bk * cper;
+    double *dst = full + bk * fper;
+    const int tid = threadIdx.x;
+    const bool pairs = !(n & 1) && !((reinterpret_cast<unsigned long long>(compact) | reinterpret_cast<unsigned long long>(full)) & 15ull);
+    if (r < S) {
+        const int c0 = r * cpi, c1 = min(cols, c0 + cpi);
+        if (pairs) {
+            const int nn2 = (int)(nn >> 1);  // n <= 64: at most 2048 pairs = 8 per thread
+            double2_t v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (tid + 256 * q < nn2) v[q] = *reinterpret_cast<const double2_t *>(src + 2 * (tid + 256 * q));
+            double *o = dst + (long long)c0 * nn;
+            for (int c = c0; c < c1; ++c, o += nn) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    if (tid + 256 * q < nn2) *reinterpret_cast<double2_t *>(o + 2 * (tid + 256 * q)) = v[q];
+            }
+        } else {
+            for (int e = tid; e < nn; e += 256) {
+                const double v = src[e];
+                for (int c = c0; c < c1; ++c) dst[(long long)c * nn + e] = v;
+            }
+        }
+    } else {
+        const long long e0 = (long long)(r - S) * 4096, e1 = min(tail, e0 + 4096);
+        src += nn;
+        double *ones = dst + cols * nn;
+        dst = ones + xd;
+        if (pairs) {
+            for (long long e = e0 + 2 * tid; e < e1; e += 512) *reinterpret_cast<double2_t *>(dst + e) = *reinterpret_cast<const double2_t *>(src + e);
+            if (r == S)
+                for (long long e = 2 * tid; e < xd; e += 512) *reinterpret_cast<double2_t *>(ones + e) = double2_t{1.0, 1.0};
+        } else {
+            for (long long e = e0 + tid; e < e1; e += 256) dst[e] = src[e];
+            if (r == S)
+                for (long long e = tid; e < xd; e += 256) ones[e] = 1.0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Rollout: exact piecewise-constant propagation  X_{k+1} = exp(dt_k G(u_k)) X_k  from the knot-0 state
 // -- what the reference's unitary_rollout(...; interpolation = :constant) integrates with an ODE solver

@@ -10,6 +10,7 @@
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
 //   pcl_kernel_exp.hpp         the exact exponential integrator (PCL_ORDER_EXP): residual and Jacobian through Frechet pairs
 //   pcl_kernel_exp_hess.hpp    ... its Hessian of the Lagrangian (option exp_hess): second Frechet derivatives, one chain per drive
+//   pcl_kernel_exp_merit.hpp   ... its reduce payload without the Jacobian (option exp_full): one adjoint pair chain per interval
 //   pcl_kernel_var_exp_hess.hpp ... the same of a variational context (option var_exp_hess): third Frechet derivatives, an octuple chain per (variation, drive)
 //   pcl_kernel_var_exp_hess_tiles.hpp ... its octuple chain with four tiles in a device workspace (option var_exp_hess_tiles): generator dimensions 46 .. 62
 //   pcl_kernel_var_exp.hpp     the variational integrators on the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): residual and Jacobian
@@ -50,8 +51,9 @@
 #include "pcl_kernel_hessian_v3.hpp"
 #include "pcl_kernels_misc.hpp"
 #include "pcl_kernels_objective.hpp"
-#include "pcl_kernel_exp.hpp"
 #include "pcl_kernel_exp_hess.hpp"
+#include "pcl_kernel_exp.hpp"  // (its payload variant reduces with the Hessian kernel's exph_block_sum)
+#include "pcl_kernel_exp_merit.hpp"
 #include "pcl_host_expand.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -64,8 +66,9 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
-    int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order, no compact Jacobian, the Hessian by option
+    int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
+    int exp_full = 0;            // ... option exp_full: the compact Jacobian trio, the host expansion and the merit / reduce payload are served
     double *dexph = nullptr;     // ... its workspace: [G(u_k) | W_k | norm] per (member, interval)
     long long exph_cap = 0;
     int var = 0;  // PCL_BATCH_VARIATIONAL: the number of variations v (x_dim is then the stacked (1 + v) x_dim of the components)
@@ -332,7 +335,10 @@ static long long jac_per_full(const pcl_ctx *c) {
     if (c->exp) return (long long)c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 2);  // -E copies | the diagonal of I | tails
     return 2LL * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
-static long long jac_per_compact(const pcl_ctx *c) { return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1); }
+static long long jac_per_compact(const pcl_ctx *c) {
+    if (c->exp) return (long long)c->n * c->n + c->x_dim * (c->desc.n_drives + 1);  // -E | tails (option exp_full)
+    return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
+}
 static long long hess_per(const pcl_ctx *c) {
     const long long m = c->desc.n_drives;
     if (c->exp || c->vexp) return (m + 1) * (m + 2) / 2 + c->x_dim * (m + 1);  // nothing involves X_{k+1}
@@ -359,8 +365,8 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 #include "pcl_host_variational.hpp"
 
 // The exponential mode (PCL_ORDER_EXP) serves the residual, the Jacobian, the rollout and the objective family.  The compact Jacobian and the
-// merit / reduce payload are refused in these words, and so is the Hessian of the Lagrangian (its (u_i, u_j) block needs second Frechet
-// derivatives: pcl_kernel_exp_hess.hpp) unless the context's option exp_hess is on.
+// merit / reduce payload are refused in these words unless the context's option exp_full is on, and so is the Hessian of the Lagrangian (its
+// (u_i, u_j) block needs second Frechet derivatives: pcl_kernel_exp_hess.hpp) unless its option exp_hess is.
 #define EXP_NOTIMPL(ctx, what)                                                                                                                      \
     do {                                                                                                                                            \
         if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
@@ -369,6 +375,11 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 #define EXP_HESS_GATE(ctx, what)                       \
     do {                                               \
         if ((ctx) && !(ctx)->exp_hess) EXP_NOTIMPL(ctx, what); \
+    } while (0)
+// ... and the compact Jacobian trio and the merit / reduce entry points unless its option exp_full is on
+#define EXP_FULL_GATE(ctx, what)                       \
+    do {                                               \
+        if ((ctx) && !(ctx)->exp_full) EXP_NOTIMPL(ctx, what); \
     } while (0)
 
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
@@ -736,7 +747,7 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
     VAR_NOTIMPL(ctx, "pcl_jac_compact_nnz");
-    EXP_NOTIMPL(ctx, "pcl_jac_compact_nnz");
+    EXP_FULL_GATE(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
     if (nnz) *nnz = jac_per_compact(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
@@ -1398,9 +1409,17 @@ static int launch_pade_general(pcl_ctx *ctx, KParams &p, bool want_jac) {
     return PCL_OK;
 }
 
+// the payload's partial sums, (m + 2) per (member, interval), and phi per (output set, interval)
+static int merit_scratch(pcl_ctx *ctx) {
+    const pcl_desc &D = ctx->desc;
+    const int sets = D.batch_mode == PCL_BATCH_TRAJ ? D.batch : 1;
+    if (!ctx->dphik) HIP_TRY(ctx, hipMalloc((void **)&ctx->dphik, ((size_t)D.batch * ctx->K * (D.n_drives + 2) + (size_t)sets * ctx->K) * sizeof(double)));
+    return PCL_OK;
+}
+
 // The exponential mode: one workgroup per (member, interval, drive) for residual + Jacobian, per (member, interval) for the residual alone
 // (pcl_kernel_exp.hpp).  G_l has an LDS tile of its own where the five tiles and the X_k tile fit.
-static int launch_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
+static int launch_exp(pcl_ctx *ctx, KParams &p, bool want_jac, int mode = 0) {
     const size_t tile = (size_t)p.LD * p.n;
     const bool fre = want_jac && p.m > 0;
     size_t dbl = (want_jac ? 4 : 3) * tile + (size_t)p.LD * p.cols + 32 + 64;
@@ -1411,12 +1430,16 @@ static int launch_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
     const long long grid = (long long)p.batch * p.K * (want_jac ? std::max(p.m, 1) : 1);
     if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
     typedef void (*kexp_t)(const KParams, const double *, int);
-    const kexp_t kern = want_jac ? (kexp_t)pcl_exp_kernel<true> : (kexp_t)pcl_exp_kernel<false>;
+    // mode (option exp_full): the compact values, or the full values with the payload's partial sums (pcl_kernel_exp.hpp)
+    const kexp_t kern = !want_jac ? (kexp_t)pcl_exp_kernel<false>
+                        : mode == PCL_EXP_COMPACT ? (kexp_t)pcl_exp_kernel<true, PCL_EXP_COMPACT>
+                        : mode == PCL_EXP_MERIT   ? (kexp_t)pcl_exp_kernel<true, PCL_EXP_MERIT>
+                                                  : (kexp_t)pcl_exp_kernel<true>;
     if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 0 : 2, lds)) return rc;
     const unsigned threads = p.n > 32 ? 512 : 256;  // (more than eight 16 x 16 output tiles per product: eight waves, a pair of tiles each)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, ctx->stream, p, (const double *)ctx->dGjd, gl_lds);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->last_kernel = want_jac ? 100 : 101;  // the exponential kernel: fused | residual only
+    ctx->last_kernel = !want_jac ? 101 : (mode == PCL_EXP_COMPACT ? 102 : 100);  // the exponential kernel: fused | residual only | compact
     ctx->last_n_stream = 0;
     return PCL_OK;
 }
@@ -1475,7 +1498,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
         return var_launch_fused(ctx, Z, delta, jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
-    if (ctx->exp && compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
+    if (ctx->exp && compact && !ctx->exp_full) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
     KParams p;
     fill_params(ctx, p);
     p.Z = Z + (ctx->desc.batch_mode == PCL_BATCH_TRAJ ? (long long)ctx->win_first * ctx->desc.z_dim * ctx->desc.N : 0);
@@ -1484,7 +1507,18 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
-    if (ctx->exp) return launch_exp(ctx, p, want_jac);
+    if (ctx->exp) {
+        if (want_jac && compact) return launch_exp(ctx, p, true, PCL_EXP_COMPACT);
+        // the payload-fused call (pcl_eval_jac_merit_dev, option exp_full): every member, so that the partial sums are numbered as the sum kernel reads them
+        if (want_jac && ctx->merit_want && ctx->exp_full && delta && ctx->win_first == 0 && ctx->win_count == ctx->desc.batch) {
+            if (int rc = merit_scratch(ctx)) return rc;
+            p.mpart = ctx->dphik;
+            p.mlam = ctx->merit_lam;
+            ctx->merit_fused = 1;
+            return launch_exp(ctx, p, true, PCL_EXP_MERIT);
+        }
+        return launch_exp(ctx, p, want_jac);
+    }
     // streaming stores of the Jacobian blocks (auto): write-through while the launch's values fit the infinity cache with room to
     // spare (one trajectory of config 3: 133 MB), plain write-back above (see store2)
     if (ctx->opt_nt < 0 && want_jac && !compact && (long long)ctx->win_count * ctx->K * jac_per_full(ctx) * 8 <= (192LL << 20)) p.nt = 2;
@@ -2368,16 +2402,25 @@ extern "C" int pcl_jac_dev(pcl_ctx *ctx, const double *Z, double *vals) {  // ev
 extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *delta, double *compact) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !compact) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_compact_dev: NULL pointer");
-    EXP_NOTIMPL(ctx, "pcl_eval_jac_compact_dev");
+    EXP_FULL_GATE(ctx, "pcl_eval_jac_compact_dev");
     return launch_fused(ctx, Z, delta, compact, true);
 }
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
     VAR_NOTIMPL(ctx, "pcl_jac_expand_dev");
-    EXP_NOTIMPL(ctx, "pcl_jac_expand_dev");
+    EXP_FULL_GATE(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
     const long long n_bk = (long long)ctx->win_count * ctx->K;
+    if (ctx->exp) {  // [-E | tail] -> [-E x cols | ones | tail], at every column count (one column: the ones are not part of the compact block)
+        const int cpi = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_cols_per_slice > 0 ? ctx->opt_cols_per_slice : 3, ctx->cols));
+        const long long tail = (long long)ctx->x_dim * (ctx->desc.n_drives + 1);
+        const long long grid = n_bk * ((ctx->cols + cpi - 1) / cpi + (tail + 4095) / 4096);
+        if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid);
+        hipLaunchKernelGGL(pcl_exp_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, compact, vals, ctx->cols, ctx->n, ctx->desc.n_drives, n_bk, cpi);
+        HIP_TRY(ctx, hipGetLastError());
+        return PCL_OK;
+    }
     if (ctx->cols == 1) {  // one state column (kets, compact density vectors): the compact layout IS the full layout
         HIP_TRY(ctx, hipMemcpyAsync(vals, compact, (size_t)(n_bk * jac_per_full(ctx)) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         return PCL_OK;
@@ -2477,7 +2520,8 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const auto t_begin = std::chrono::steady_clock::now();
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var && !ctx->exp;  // (variational and exponential contexts: full values, host_path 1)
+    // (variational contexts, and exponential ones without the option exp_full: full values, host_path 1)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var && (!ctx->exp || ctx->exp_full);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -2514,14 +2558,18 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
         if (!ctx->pool) return fail(ctx, PCL_ENOMEM, "thread pool");
     }
     const int cols = ctx->cols;
-    const long long nn = (long long)ctx->n * ctx->n, tail = ctx->x_dim * (ctx->desc.n_drives + 1);
+    const long long nn = (long long)ctx->n * ctx->n, tail = ctx->x_dim * (ctx->desc.n_drives + 1), xd = ctx->x_dim;
+    const bool expo = ctx->exp != 0;
     const double *hc = ctx->hcompact;
     int store_w = 0;
     const pcl_host::stream_copy_fn copy = pcl_host::pick_stream_copy((int)ctx->opt_host_store_bytes, &store_w);
     ctx->last_host_store_bytes = store_w;
     ctx->pool->begin(2 * nbk, [=](long long job) {
         const long long bk = job >> 1;
-        pcl_host::expand_interval(vals + bk * fper, hc + bk * cper, cols, nn, tail, (int)(job & 1), copy);
+        if (expo)
+            pcl_host::expand_interval_exp(vals + bk * fper, hc + bk * cper, cols, nn, xd, tail, (int)(job & 1), copy);
+        else
+            pcl_host::expand_interval(vals + bk * fper, hc + bk * cper, cols, nn, tail, (int)(job & 1), copy);
     });
     int rc = PCL_OK;
     for (int c = 0; c < n_chunks; ++c) {

@@ -39,25 +39,31 @@ def init_process_group(backend=None):
     return dist
 
 
-def jacobian_views(vals, batch, K, d, m, cols=None):
+def jacobian_views(vals, batch, K, d, m, cols=None, exponential=False):
     """View into the Jacobian value buffer (order: include/piccolo_hip.h): the tail as
-    ``[batch, K, cols, m+1, n]`` (state column, drive l or dt at index m, row) without copying."""
+    ``[batch, K, cols, m+1, n]`` (state column, drive l or dt at index m, row) without copying.
+    ``exponential=True``: the layout of a context of the exponential constraint (``pade_order="exp"``) -- ``cols`` copies of ``-E``, then the
+    ``x_dim`` ones of ``d delta / d X_{k+1}``, then the same tail."""
     C = d if cols is None else cols
     n = 2 * d
+    if exponential:
+        head = C * n * n + n * C
+        v = vals.view(batch, K, head + n * C * (m + 1))
+        return v[:, :, head:].reshape(batch, K, C, m + 1, n)
     per = 2 * C * n * n + n * C * (m + 1)
     v = vals.view(batch, K, per)
     return v[:, :, 2 * C * n * n :].reshape(batch, K, C, m + 1, n)
 
 
-def constraint_merit_and_shared_gradient(delta, vals, batch, K, d, m, weights=None, cols=None):
+def constraint_merit_and_shared_gradient(delta, vals, batch, K, d, m, weights=None, cols=None, exponential=False):
     """phi = sum_i w_i/2 |delta_i|^2 over this rank's members and its gradient with respect to the
     shared variables: g_u[k, l] = sum_i w_i <d delta_ik / d u_l, delta_ik>, g_dt[k] likewise.
-    Works on any device (torch ops on views of the evaluator's output buffers)."""
+    Works on any device (torch ops on views of the evaluator's output buffers).  ``exponential``: as for ``jacobian_views``."""
     C = d if cols is None else cols
     n = 2 * d
     dl = delta.view(batch, K, C, n)
     w = torch.ones(batch, dtype=delta.dtype, device=delta.device) if weights is None else weights.to(delta)
-    tail = jacobian_views(vals, batch, K, d, m, cols)
+    tail = jacobian_views(vals, batch, K, d, m, cols, exponential)
     phi = 0.5 * torch.einsum("b,bkci,bkci->", w, dl, dl)
     g = torch.einsum("b,bkcli,bkci->kl", w, tail, dl)  # [K, m+1]
     return phi, g[:, :m].contiguous(), g[:, m].contiguous()

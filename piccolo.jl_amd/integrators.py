@@ -60,13 +60,25 @@ def _exp_hessian_value(exp_hessian):
     raise ValueError("exp_hessian must be False, True or \"workspace\" (got %r)" % (exp_hessian,))
 
 
+def _check_exp_full(exp_full, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``exp_full`` (the library's option of that name) belongs to a plain context of the exponential constraint: anything else is a
+    ``ValueError``, before any device call."""
+    if not exp_full:
+        return
+    if _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
+        raise ValueError("exp_full=True serves the compact Jacobian and the merit / reduce payload of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("exp_full=True is not served on a variational context")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
-                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False):  # fmt: skip
+                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False):  # fmt: skip
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
+        _check_exp_full(exp_full, pade_order, batch_mode)
         if exp_hessian and pade_order != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         if exp_hessian == "workspace" and batch_mode != PCL_BATCH_VARIATIONAL_EXP:
@@ -102,11 +114,14 @@ class _PclContext:
         self.x_dim, self.n_rows, self.n_cols = a.value, b.value, c.value
         self._chk(self._L.pcl_jac_nnz(h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz, self.jac_per = a.value, b.value
-        # the exponential constraint: no compact Jacobian, and no Hessian of the Lagrangian (hess_structure / hess raise with the library's
-        # message) unless ``exp_hessian`` switches the library's option exp_hess on
+        # the exponential constraint: no compact Jacobian and no merit / reduce payload unless ``exp_full`` switches the library's option
+        # exp_full on, and no Hessian of the Lagrangian (hess_structure / hess raise with the library's message) unless ``exp_hessian``
+        # switches exp_hess on
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         self.exp_hessian = False  # (follows the library's option: set_option keeps it and hess_nnz / hess_per current)
+        self.exp_full = False  # (the same: set_option keeps it and compact_nnz / compact_per current)
         self.hess_nnz = self.hess_per = 0
+        self.compact_nnz = self.compact_per = 0
         if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
             self.set_option("var_exp_hess_tiles", 1)
         if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
@@ -116,9 +131,10 @@ class _PclContext:
         else:
             self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
-        if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) or self.exponential:  # (no compact Jacobian for the stacked state)
-            self.compact_nnz = self.compact_per = 0
-        else:
+        if exp_full:
+            self.set_option("exp_full", 1)
+        # (no compact Jacobian for the stacked state; the exponential constraint's by ``exp_full`` only: set_option has the sizes)
+        if batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) and not self.exponential:
             self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
             self.compact_nnz, self.compact_per = a.value, b.value
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
@@ -269,7 +285,10 @@ class _PclContext:
         if self.exp_hessian:
             self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz = a.value
-        if self.exponential:  # (no compact Jacobian; the Hessian of the Lagrangian by ``exp_hessian`` only)
+        if self.exponential:  # (the compact Jacobian by ``exp_full`` only, the Hessian of the Lagrangian by ``exp_hessian`` only)
+            if self.exp_full:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+                self.compact_nnz = a.value
             return
         self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.hess_nnz = a.value
@@ -384,7 +403,8 @@ class _PclContext:
 
     def eval_jac_merit_dev(self, Z, lam, delta, vals, out):
         """``eval_jac_dev`` + ``merit_grad_dev`` in one pass over the state columns (pcl_eval_jac_merit_dev): the fused kernel
-        forms the payload's dot products while a column's vectors are in LDS; same outputs as the two calls."""
+        forms the payload's dot products while a column's vectors are in LDS; same outputs as the two calls.  ``vals=None`` (an exponential
+        context with ``exp_full`` only): the residual and the payload without the Jacobian, one adjoint chain per interval."""
         self._chk(self._L.pcl_eval_jac_merit_dev(self._h, _ptr(Z), _ptr(lam), _ptr(delta), _ptr(vals), _ptr(out)))
 
     def eval_jac_merit_objective_dev(self, Z, lam, delta, vals, out, Q, value, grad):
@@ -431,6 +451,12 @@ class _PclContext:
             if self.exp_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
+        if self.exponential and key == "exp_full":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
+            self.exp_full = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.exp_full:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.compact_nnz, self.compact_per = a.value, b.value
 
     def get_option(self, key):
         v = ctypes.c_int64()
@@ -486,7 +512,8 @@ class HipPadeIntegrator:
     in order -- the row order here is identical: member-major).
     """
 
-    def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False):
+    def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
+                 exp_full=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -495,8 +522,11 @@ class HipPadeIntegrator:
         the exponential constraint itself, ``x_{k+1} - exp(dt_k G(u_k)) x_k`` -- for steps too large for order 10 (``order_tol_met`` False); residual
         and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own.
         ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served too
-        (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62."""
+        (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62.
+        ``exp_full=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the compact Jacobian, the host-pointer calls' compact path and the
+        merit / reduce payload are served on that constraint too (the library's option ``exp_full``)."""
         exp_hessian = _exp_hessian_value(exp_hessian)
+        _check_exp_full(exp_full, pade_order)
         if exp_hessian == "workspace":
             raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint: a plain integrator takes False or True")
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
@@ -536,7 +566,7 @@ class HipPadeIntegrator:
             dt_off=traj.components[traj.timestep].start, x_offs=[traj.components[nm].start for nm in x_names],
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
-            state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian,
+            state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full,
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)

@@ -85,8 +85,10 @@ end
 
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
-                      exp_hessian::Bool = false)
+                      exp_hessian::Bool = false, exp_full::Bool = false)
     # state_cols: 0 unitary (n = 2d), 1 ket, -1 = PCL_STATE_VECTOR (general n x n generator on one real column, d := n)
+    (exp_full && pade_order != PCL_ORDER_EXP) &&
+        throw(ArgumentError("HipPadeIntegrator: exp_full = true serves the compact Jacobian and the merit / reduce payload of the exponential constraint: it needs pade_order = :exp"))
     (exp_hessian && pade_order != PCL_ORDER_EXP) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian = true is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order = :exp"))
     n = size(G0s[1], 1); d = state_cols == -1 ? n : n ÷ 2; m = length(Gjs)
@@ -110,6 +112,8 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     # (PCL_ORDER_EXP: no Hessian of the Lagrangian -- hess_per = 0, the structure is empty, pcl_hess is refused by the library -- unless
     #  exp_hessian switches the library's option exp_hess on, BEFORE the Hessian structure is queried; generator dimensions up to 62)
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_hess", 1))
+    # (exp_full: the library's option of that name -- the host-pointer calls below then move the compact values over PCIe and expand on the host)
+    exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
     (pade_order == PCL_ORDER_EXP && !exp_hessian) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
@@ -173,8 +177,10 @@ end
 # pade_order = :exp (or PCL_ORDER_EXP = -1): the exponential constraint itself, x_{k+1} - exp(dt_k G(u_k)) x_k -- for steps too large for
 # order 10; residual and Jacobian only (solve with eval_hessian = false, the reference's default).  Never chosen on its own.
 # exp_hessian = true (with pade_order = :exp only): the Hessian of the Lagrangian of that constraint too (the library's option exp_hess:
-# second Frechet derivatives of exp on the device), so the reference's templates can run with eval_hessian = true.  This glue has not been
-# executed (there is no Julia on the build or test machines), as the rest of this file.
+# second Frechet derivatives of exp on the device), so the reference's templates can run with eval_hessian = true.
+# exp_full = true (with pade_order = :exp only): the library's option exp_full -- pcl_eval_jac / pcl_jac deliver the Jacobian values through
+# the compact path (one -E per interval over PCIe, replicated by the host's threads) with the bits of the full path, and the compact /
+# merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
