@@ -162,7 +162,9 @@ typedef enum pcl_status {
                                pcl_clear_regularizers (any component of the knot), pcl_set_weights, pcl_objective[_dev],
                                pcl_objective_hess_nnz / _structure / [_dev] and pcl_rollout[_dev]; see their comments.  Setting the option
                                back to 0 restores the refusals and drops goal, weights and regularisers.  pcl_infidelity_dev, the merit /
-                               reduce entry points, the member window and the compact Jacobian stay PCL_ENOTIMPL whatever the option says.
+                               reduce entry points and the member window stay PCL_ENOTIMPL whatever the option says; so does the compact
+                               Jacobian trio unless the context's option "var_compact" = 1 serves it (see pcl_jac_compact_nnz; the host-pointer
+                               calls then deliver through the compact values where C > 1; "last_kernel" reads 72 after a compact launch).
                                The sensitivity term is evaluated at the TERMINAL knot only (the reference's own use, materialize.jl:306-307). */
 
 #define PCL_BATCH_VARIATIONAL_EXP 3 /* the same integrators on the EXACT exponential constraint x'_{k+1} = exp(dt_k Ghat) x'_k of the lifted generator
@@ -186,7 +188,8 @@ typedef enum pcl_status {
                                family and pcl_rollout[_dev] exactly as on a PCL_BATCH_VARIATIONAL context, with its bits.  PCL_ENOTIMPL, naming
                                the mode: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64] and option "exp_hess" = 1 (the Hessian of the
                                Lagrangian needs third Frechet derivatives: solve with a quasi-Newton Hessian) unless option "var_exp_hess" = 1
-                               is set (generator dimensions up to 44; see pcl_hess), the compact Jacobian trio, the
+                               is set (generator dimensions up to 44; see pcl_hess), the compact Jacobian trio unless option "var_compact" = 1
+                               is set (see pcl_jac_compact_nnz; "last_kernel" 112 after a compact launch), the
                                merit / reduce entry points, the member window, pcl_infidelity_dev.  pcl_set_order_policy and
                                pcl_set_order_from_trajectory: PCL_EINVAL (there is no order to choose).  "var_block_wgs" / "var_col_wgs" have no
                                effect.  get_option "pade_order" reads -1, "variations" v, "last_kernel" 110 (residual + Jacobian) or 111
@@ -299,7 +302,13 @@ int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count);
  * [-B^+ (n*n) | B^- (n*n) | d/du (m*x_dim) | d/ddt (x_dim)] = 2 n^2 + x_dim (m+1) doubles are unique.
  * pcl_eval_jac_compact_dev writes those; pcl_jac_expand_dev replicates them into the full triplet order.
  * A context of the exponential constraint with option "exp_full" = 1 (see PCL_ORDER_EXP): [-E (n*n) | tail (x_dim*(m+1))] = n^2 + x_dim (m+1)
- * doubles per (b,k); the expansion writes cols copies of -E, the x_dim ones of d delta / d X_{k+1}, then the tail. */
+ * doubles per (b,k); the expansion writes cols copies of -E, the x_dim ones of d delta / d X_{k+1}, then the tail.
+ * A variational context with option "var_compact" = 1 (either constraint kind; one stacked trajectory, x_dim' = (1 + v) n C), per interval:
+ *   PCL_BATCH_VARIATIONAL      [-B^+ | B^- | for i = 1..v: -L^+_i | L^-_i | tails]   (2 + 2v) n^2 + x_dim' (m+1) doubles
+ *   PCL_BATCH_VARIATIONAL_EXP  [-E | -L_1 .. -L_v | tails]                           (1 + v) n^2 + x_dim' (m+1) doubles
+ * the tails being the x_dim' (m+1) values of the full layout in its order.  The expansion writes every tile to its C copies in every segment
+ * where it occurs (-B^+, B^-, -E once per component), the x_dim' ones (exponential) and the tails -- at C = 1 too, where the compact layout
+ * still is not the full one.  Expanded values and delta have the bits of pcl_eval_jac_dev.  Without the option: PCL_ENOTIMPL. */
 int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *nnz_per_interval);
 int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z_dev, double *delta_dev, double *compact_dev);
 int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact_dev, double *vals_dev);
@@ -433,6 +442,8 @@ int pcl_comm_destroy(pcl_ctx *ctx);
  *   "v4_ticket"     launches of several trajectories: -1 auto | 0 static split | 1 groups of workgroups + slice tickets
  *   "exp_full"      contexts of the exponential constraint only (1 on any other context: PCL_EINVAL): 1 serves the compact Jacobian trio, the compact
  *                   host-pointer path and the merit / reduce entry points (see PCL_ORDER_EXP); 0 (default) refuses them
+ *   "var_compact"   variational contexts only, either constraint kind (1 on any other context: PCL_EINVAL): 1 serves the compact Jacobian trio and
+ *                   the compact host-pointer path (see pcl_jac_compact_nnz); 0 (default) refuses them.  Independent of "var_full" / "var_exp_hess"
  *   "var_full"      variational contexts only (1 on any other context: PCL_EINVAL): 1 serves the objective entry points and the rollout
  *                   (see PCL_BATCH_VARIATIONAL); 0 (default) refuses them and drops goal, weights and regularisers
  * and reads: "pade_order" (the order in use), "last_kernel" / "last_hess_kernel" (which kernel family ran), "jit_compiles", "jit_cache_hits",

@@ -156,6 +156,35 @@ static inline void expand_interval_exp(double *__restrict__ full, const double *
     }
 }
 
+// The same for a variational context (option var_compact).  The full block is a run of segments, cols copies of one compact tile each, then the
+// tail: job q = segment * cols + copy; half 0 takes the first half of the jobs, half 1 the rest and what follows the segments.
+//   Pade: compact [-B+ | B- | per variation i: -L+_i | L-_i | tail] -> segments [-B+, B-, per i: -B+, B-, -L+_i, L-_i]
+static inline int var_tile_of_segment(int s) {
+    if (s < 2) return s;
+    const int i = (s - 2) >> 2, j = (s - 2) & 3;
+    return j < 2 ? j : 2 * i + j;
+}
+static inline void expand_interval_var(double *__restrict__ full, const double *__restrict__ compact, int cols, long long nn, int v, long long tail, int half,
+                                       stream_copy_fn copy) {
+    const long long jobs = (2LL + 4LL * v) * cols, mid = (jobs + 1) / 2;
+    for (long long q = half ? mid : 0; q < (half ? jobs : mid); ++q) copy(full + q * nn, compact + var_tile_of_segment((int)(q / cols)) * nn, (size_t)nn);
+    if (half) copy(full + jobs * nn, compact + (2LL + 2LL * v) * nn, (size_t)tail);
+}
+//   exponential: compact [-E | -L_1 .. -L_v | tail] -> segments [-E, per i: -E, -L_i], the ones (xd) and the tail
+static inline void expand_interval_var_exp(double *__restrict__ full, const double *__restrict__ compact, int cols, long long nn, int v, long long xd, long long tail,
+                                           int half, stream_copy_fn copy) {
+    const long long jobs = (1LL + 2LL * v) * cols, mid = (jobs + 1) / 2;
+    for (long long q = half ? mid : 0; q < (half ? jobs : mid); ++q) {
+        const int s = (int)(q / cols);
+        copy(full + q * nn, compact + ((s & 1) ? 0 : s >> 1) * nn, (size_t)nn);  // segment 2 i - 1: -E; segment 2 i: -L_i
+    }
+    if (half) {
+        double *ones = full + jobs * nn;
+        for (long long e = 0; e < xd; ++e) ones[e] = 1.0;
+        copy(ones + xd, compact + (1LL + v) * nn, (size_t)tail);
+    }
+}
+
 // CPUs the cgroup grants this process (cpu.max = "quota period", cgroup v2; cfs_quota_us / cfs_period_us, v1); 0: no quota.  A container may see
 // 256 hardware threads and be allowed 16 CPUs' worth of time: a team above the quota wins single calls and is throttled over a run.
 static inline double cgroup_quota_cpus() {

@@ -35,6 +35,11 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_full = 1 needs a plain context of the exponential constraint (PCL_ORDER_EXP, not a variational one)");
         ctx->exp_full = (int)v;
     }
+    else if (!strcmp(key, "var_compact")) {  // variational contexts, either constraint kind: serve the compact Jacobian trio and the host expansion (0: refuse them, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_compact must be 0 or 1");
+        if (v && !ctx->var) return fail(ctx, PCL_EINVAL, "var_compact = 1 needs a variational context (PCL_BATCH_VARIATIONAL or PCL_BATCH_VARIATIONAL_EXP)");
+        ctx->var_compact = (int)v;
+    }
     else if (!strcmp(key, "var_exp_hess")) {  // variational contexts of the exponential constraint: serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_exp_hess must be 0 or 1");
         if (v)
@@ -184,6 +189,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->exp_hess;
     else if (!strcmp(key, "exp_full"))
         *v = ctx->exp_full;
+    else if (!strcmp(key, "var_compact"))
+        *v = ctx->var_compact;
     else if (!strcmp(key, "var_exp_hess"))
         *v = ctx->var_exp_hess;
     else if (!strcmp(key, "var_exp_hess_tiles"))

@@ -375,7 +375,7 @@ static int var_split_cols(const pcl_ctx *ctx) {
 
 // PCL_BATCH_VARIATIONAL_EXP (pcl_kernel_var_exp.hpp): the preparation launch (G(u_k) and its norm per interval), then one workgroup per
 // (interval, variation, drive) for residual + Jacobian, per (interval, variation) for the residual alone.
-static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals, bool compact) {
     const pcl_desc &D = ctx->desc;
     const int n = ctx->n, m = D.n_drives, v = ctx->var;
     const size_t nn = (size_t)n * n;
@@ -400,7 +400,8 @@ static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *
     p.Gj = ctx->dvar_tab + nn;
     p.Gv = ctx->dvar_tab + (1 + m) * nn;
     p.ws = ctx->dexph;
-    p.jper = var_jac_per(ctx);
+    p.jper = compact ? jac_per_compact(ctx) : var_jac_per(ctx);
+    p.compact = compact ? 1 : 0;
     p.n = n;
     p.LD = ((n + 3) & ~3) + 2;
     p.cols = ctx->cols;
@@ -419,7 +420,7 @@ static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *
     const unsigned threads = n > 32 ? 512 : 256;  // (as the exponential kernels: a pair of output tiles per wave)
     void *args[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3(threads), args, lds, ctx->stream));
-    ctx->last_kernel = jac ? 110 : 111;
+    ctx->last_kernel = jac ? (compact ? 112 : 110) : 111;  // the variational exponential kernel: fused | residual only | compact
     return PCL_OK;
 }
 
@@ -548,9 +549,9 @@ static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, 
     return PCL_OK;
 }
 
-static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals, bool compact = false) {
     ON_DEVICE(ctx);
-    if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals);
+    if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals, compact);
     if (ctx->desc.pade_order == 0)
         return fail(ctx, PCL_EINVAL, "pcl_eval / pcl_jac: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
     VarParams p;
@@ -559,7 +560,8 @@ static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double
     p.delta = delta;
     p.vals = vals;
     const bool jac = vals != nullptr;
-    p.nbw = jac ? var_split_blocks(ctx) : 0;
+    p.nbw = jac ? (compact ? 1 : var_split_blocks(ctx)) : 0;  // (a compact launch stores every tile once: nothing to split)
+    if (compact) p.compact = 1, p.jper = jac_per_compact(ctx);
     p.ncw = var_split_cols(ctx);
     const void *f = var_pick_fused(ctx->var, ctx->desc.pade_order / 2, jac);
     if (!f) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: no variational kernel for v=%d, order %d", ctx->var, ctx->desc.pade_order);
@@ -571,7 +573,7 @@ static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double
     if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
     void *args[] = {&p};
     HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3(PCL_VAR_THREADS), args, lds, ctx->stream));
-    ctx->last_kernel = jac ? 70 : 71;
+    ctx->last_kernel = jac ? (compact ? 72 : 70) : 71;  // the variational kernel: fused | residual only | compact
     return PCL_OK;
 }
 
@@ -611,6 +613,11 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
     do {                                                                                                                               \
         if ((ctx) && (ctx)->var)                                                                                                       \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (%s)", what, (ctx)->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL"); \
+    } while (0)
+// The compact Jacobian trio: refused in the same words unless the context's option var_compact is on.
+#define VAR_COMPACT_GATE(ctx, what)                                   \
+    do {                                                              \
+        if ((ctx) && (ctx)->var && !(ctx)->var_compact) VAR_NOTIMPL(ctx, what); \
     } while (0)
 // The objective and the rollout: refused in the same words unless the context's option var_full is on (pcl_host_robust.hpp serves them then).
 #define VAR_GATE(ctx, what)                                        \

@@ -17,7 +17,8 @@
 //                             of the first variation also store component 0's slice l; workgroup (i, 0) adds delta_i, the dt tail and the ones of
 //                             component i, workgroup (1, 0) those of component 0.  The copies of -E (every workgroup of the interval has E) and of
 //                             -L_i (the workgroups of variation i) are dealt round-robin over the workgroups that hold the tile, 16-byte stores.
-//                             m = 0: the pair (T, Tp) alone.
+//                             m = 0: the pair (T, Tp) alone.  A compact launch (VarExpParams::compact) stores [-E | -L_1 .. -L_v | tails]:
+//                             -E once, by workgroup (1, 0); -L_i once, by workgroup (i, 0); no ones; the tails right behind the tiles.
 //   pcl_var_exp_kernel<false> residual only: one workgroup per (interval, variation), the pair alone -- the same T and Tp recurrences and the same
 //                             products Y_0, Y_i, hence the delta bits of the fused launch.
 // LDS: five rotating n x n tiles (T, Tp, Tq, Tw, scratch); G(u_k) has a sixth where that fits (n <= 56) and is read from the workspace through L2
@@ -35,6 +36,7 @@ struct VarExpParams {
     long long jper;
     int n, LD, cols, m, K, v, z_dim, u_off, dt_off;
     int g_lds;  // G(u_k) has a tile of its own
+    int compact;  // option var_compact: the values are [-E | -L_1 .. -L_v | tails], every tile once and no ones
     int xo[PCL_VAR_MAXV + 1];
 };
 
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(512) void pcl_var_exp_kernel(const VarExpParams p) 
     }
     __syncthreads();
     double *jv = JAC ? p.vals + (long long)k * p.jper : nullptr;
-    const long long seg1 = (1LL + 2 * v) * cols * nn, tail0 = seg1 + xd;
+    const long long seg1 = (1LL + 2 * v) * cols * nn, tail0 = p.compact ? (1LL + v) * nn : seg1 + xd;
     const int tw = (m + 1) * n;  // tail doubles per state column
     double *t0 = JAC ? jv + tail0 : nullptr, *ti = JAC ? t0 + (long long)(1 + iv) * cols * tw : nullptr;  // the tails of component 0 and of component i
     if (fre) {  // the accumulators go to the values: column c of the product is state column c's slice l
@@ -218,13 +220,18 @@ __global__ __launch_bounds__(512) void pcl_var_exp_kernel(const VarExpParams p) 
             gemm_lds_acc<false, false>(Gvi, n, Y0, LD, ti + m * n, tw, n, cols, n, -1.0);
             vexp_g<true>(Gt, Gg, Yi, ti + m * n, tw, LD, n, cols, -1.0);
             if (iv == 0) vexp_g<false>(Gt, Gg, Y0, t0 + m * n, tw, LD, n, cols, -1.0);
-            for (int e = tid; e < ne; e += nth) {  // the identity's diagonal
+            for (int e = tid; e < ne && !p.compact; e += nth) {  // the identity's diagonal (the expansion writes it for a compact launch)
                 if (iv == 0) jv[seg1 + e] = 1.0;
                 jv[seg1 + (1 + iv) * xdc + e] = 1.0;
             }
         }
     }
-    if (JAC) {
+    if (JAC && p.compact) {
+        if (l == 0) {
+            if (iv == 0) vexp_store_neg(jv, T, LD, n);
+            vexp_store_neg(jv + (1LL + iv) * nn, Tp, LD, n);
+        }
+    } else if (JAC) {
         // blocks: -E (component 0) | per variation: -E, -L_i -- cols copies each.  The 1 + v blocks of -E are dealt over all v ml workgroups of
         // the interval, the block of -L_i over the ml workgroups of variation i.
         const int w = iv * ml + l, W = v * ml;

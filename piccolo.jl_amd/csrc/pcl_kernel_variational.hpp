@@ -7,7 +7,8 @@
 //
 // Two roles per interval in one launch (pcl_var_fused_kernel):
 //   * block workgroups fold the powers P_j = G^j and the Frechet powers Q_j^i (the (i,0) block of Ghat^j: Q_1 = Gv_i, Q_j = G Q_{j-1} + Gv_i P_{j-1})
-//     into B^{+-} = sum_j T_j (+-1)^j P_j and L^{+-}_i = sum_{j>=1} T_j (+-1)^j Q_j^i, and stream their d replicated copies with 16-byte stores;
+//     into B^{+-} = sum_j T_j (+-1)^j P_j and L^{+-}_i = sum_{j>=1} T_j (+-1)^j Q_j^i, and stream their d replicated copies with 16-byte stores
+//     (a compact launch, VarParams::compact: each of the 2 + 2 v tiles once, from the same registers, and the tails right behind them);
 //   * column workgroups run one wave per state column: lane i holds row i of each of the 1 + v components, products with G / Gv_i / G_l are
 //     lane-parallel row-compressed (ELL) products: lane i sums its row's non-zeros, the entries of x fetched from their lanes.  They write delta and the tails
 //     (d delta / d u_l, d delta / d dt), from the Horner chains  R_{q-1} = T_q Y_q,  R_e = Ghat R_{e+1} + T_{e+1} Y_{e+1}:
@@ -44,6 +45,7 @@ struct VarParams {
     int xo[PCL_VAR_MAXV + 1];  // state offsets of the 1 + v components inside a knot
     int nbw, ncw;  // block / column workgroups per interval (fused kernel)
     int hw;        // waves per workgroup (Hessian kernel)
+    int compact;   // fused kernel (option var_compact): the values are [-B+ | B- | per variation: -L+_i | L-_i | tails], every tile once (nbw = 1)
     // column role: the generators row-compressed (ELL, [slot t][row i], padded with column 0 / value 0), so a product costs its
     // non-zeros per row instead of n: G(u) on the union pattern of the drift and the drives (gval: the drift's values, then each drive's),
     // the drives, the variation generators
@@ -249,10 +251,28 @@ __device__ void pcl_var_block_role(const VarParams &p, int k, int rb, double *ld
             __syncthreads();
         }
     }
+    double *base = p.vals + (size_t)k * p.jper;
+    if (p.compact) {  // [-B+ | B- | -L+_1 | L-_1 | ..]: every tile once (one block workgroup per interval)
+#pragma unroll
+        for (int s = 0; s < PCL_VAR_PPT; ++s) {
+            const int pr = tid + s * PCL_VAR_THREADS;
+            if (pr < npair) {
+                double *b0 = base + 2 * pr;
+                const pcl_var_d2 bp = E[s] + O[s], bm = E[s] - O[s];
+                *(pcl_var_d2 *)b0 = -bp;
+                *(pcl_var_d2 *)(b0 + nn) = bm;
+#pragma unroll
+                for (int v = 0; v < V; ++v) {
+                    *(pcl_var_d2 *)(b0 + (size_t)(2 + 2 * v) * nn) = -(EQ[s][v] + OQ[s][v]);
+                    *(pcl_var_d2 *)(b0 + (size_t)(3 + 2 * v) * nn) = EQ[s][v] - OQ[s][v];
+                }
+            }
+        }
+        return;
+    }
     // the copies c in [c0, c1) of every block of this interval
     const int c0 = (int)((long long)rb * C / p.nbw), c1 = (int)((long long)(rb + 1) * C / p.nbw);
     const long long segsz = (long long)C * nn;
-    double *base = p.vals + (size_t)k * p.jper;
     for (int c = c0; c < c1; ++c) {
         double *b0 = base + (size_t)c * nn;
 #pragma unroll
@@ -321,7 +341,7 @@ __device__ void pcl_var_col_role(const VarParams &p, int k, int rc, double *lds)
             for (int b = 0; b <= V; ++b) p.delta[(size_t)k * xdl + b * xdc + (size_t)c * n + lane] = t[b] + Ye[b];
         }
         if (!JAC) continue;
-        double *tail = p.vals + (size_t)k * p.jper + (size_t)(2 + 4 * V) * C * nn;
+        double *tail = p.vals + (size_t)k * p.jper + (p.compact ? (size_t)(2 + 2 * V) * nn : (size_t)(2 + 4 * V) * C * nn);
         const long long tstride = (long long)(m + 1) * n;  // per (component, column)
         // d/dh: Horner on T'_j
         double R1[V + 1];

@@ -105,6 +105,83 @@ __global__ __launch_bounds__(256) void pcl_exp_expand_kernel(const double *__res
     }
 }
 
+// The same for a variational context (option var_compact), either constraint kind; xd = (1 + v) n cols is the stacked state, tail = xd (m + 1):
+//   Pade         compact [-B+ | B- | per variation i: -L+_i | L-_i | tail] -> full [-B+ x cols | B- x cols | per i: -B+ x cols | B- x cols | -L+_i x cols | L-_i x cols | tail]
+//   exponential  compact [-E | -L_1 .. -L_v | tail]                        -> full [-E x cols | per i: -E x cols | -L_i x cols | ones (xd) | tail]
+//   per interval: (distinct tiles) x S block workgroups -- tile t, a slice of cpi state columns: the tile is read once, then stored to that slice of
+//   every segment it occurs in (-B+, B-, -E: 1 + v segments; the others: one) -- and T tail workgroups (4096 doubles each; the first also writes
+//   the ones).  n = 2 d is even, so every tile, segment and tail starts on 16 bytes where both arrays do: 16-byte accesses then, scalar otherwise.
+//   One state column (kets) takes the same path: the tiles of component 0 still repeat per variation.  Copies only: the bits of the compact values.
+__global__ __launch_bounds__(256) void pcl_var_expand_kernel(const double *__restrict__ compact, double *__restrict__ full, int cols, int n, int m, int v,
+                                                             int expo, long long n_bk, int cpi) {
+    const long long nn = (long long)n * n, xd = (long long)n * cols * (1 + v), tail = xd * (m + 1), seg = cols * nn;
+    const int ntile = expo ? 1 + v : 2 + 2 * v, nseg = expo ? 1 + 2 * v : 2 + 4 * v;
+    const long long cper = ntile * nn + tail, fper = nseg * seg + (expo ? xd : 0) + tail;
+    const int S = (cols + cpi - 1) / cpi, T = (int)((tail + 4095) / 4096);
+    const int per_bk = ntile * S + T;
+    const long long bk = blockIdx.x / per_bk;
+    const int r = (int)(blockIdx.x - bk * per_bk);
+    if (bk >= n_bk) return;
+    const double *src = compact + bk * cper;
+    double *dst = full + bk * fper;
+    const int tid = threadIdx.x;
+    const bool pairs = !(n & 1) && !((reinterpret_cast<unsigned long long>(compact) | reinterpret_cast<unsigned long long>(full)) & 15ull);
+    if (r < ntile * S) {
+        const int t = r / S, sl = r - t * S;
+        const int c0 = sl * cpi, c1 = min(cols, c0 + cpi);
+        // the segments of tile t: s0 and, for the tiles of component 0 (rep), one more per variation a = 1 .. v
+        int s0, ns;
+        bool rep;
+        if (expo) {
+            rep = t == 0;                                     // -E: segments 0 and 2 a - 1
+            s0 = rep ? 0 : 2 * t, ns = rep ? 1 + v : 1;       // -L_t: segment 2 t
+        } else {
+            rep = t < 2;                                      // -B+ / B-: segments t and 4 a - 2 + t
+            s0 = rep ? t : 4 + 4 * ((t - 2) >> 1) + (t & 1);  // -L+_i / L-_i (t = 2 i + j): segment 4 i + j
+            ns = rep ? 1 + v : 1;
+        }
+        src += t * nn;
+        if (pairs) {
+            const int nn2 = (int)(nn >> 1);  // n <= 64: at most 2048 pairs = 8 per thread
+            double2_t val[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (tid + 256 * q < nn2) val[q] = *reinterpret_cast<const double2_t *>(src + 2 * (tid + 256 * q));
+            for (int a = 0; a < ns; ++a) {
+                const int sg = a == 0 ? s0 : (expo ? 2 * a - 1 : 4 * a - 2 + s0);
+                double *o = dst + sg * seg + (long long)c0 * nn;
+                for (int c = c0; c < c1; ++c, o += nn) {
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        if (tid + 256 * q < nn2) *reinterpret_cast<double2_t *>(o + 2 * (tid + 256 * q)) = val[q];
+                }
+            }
+        } else {
+            for (int e = tid; e < nn; e += 256) {
+                const double x = src[e];
+                for (int a = 0; a < ns; ++a) {
+                    const int sg = a == 0 ? s0 : (expo ? 2 * a - 1 : 4 * a - 2 + s0);
+                    for (int c = c0; c < c1; ++c) dst[sg * seg + (long long)c * nn + e] = x;
+                }
+            }
+        }
+    } else {
+        const long long e0 = (long long)(r - ntile * S) * 4096, e1 = min(tail, e0 + 4096);
+        src += ntile * nn;
+        double *ones = dst + nseg * seg;
+        dst = ones + (expo ? xd : 0);
+        if (pairs) {
+            for (long long e = e0 + 2 * tid; e < e1; e += 512) *reinterpret_cast<double2_t *>(dst + e) = *reinterpret_cast<const double2_t *>(src + e);
+            if (expo && r == ntile * S)
+                for (long long e = 2 * tid; e < xd; e += 512) *reinterpret_cast<double2_t *>(ones + e) = double2_t{1.0, 1.0};
+        } else {
+            for (long long e = e0 + tid; e < e1; e += 256) dst[e] = src[e];
+            if (expo && r == ntile * S)
+                for (long long e = tid; e < xd; e += 256) ones[e] = 1.0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Rollout: exact piecewise-constant propagation  X_{k+1} = exp(dt_k G(u_k)) X_k  from the knot-0 state
 // -- what the reference's unitary_rollout(...; interpolation = :constant) integrates with an ODE solver

@@ -87,6 +87,7 @@ struct pcl_ctx {
     long long var_off_d = 0, var_voff_d = 0, var_off_v = 0, var_voff_v = 0;
     int64_t opt_var_blocks = 0, opt_var_cols = 0;  // ... block / column workgroups per interval of the fused launch (0 auto)
     int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
+    int var_compact = 0;         // ... option var_compact: the compact Jacobian trio and the host expansion are served (either constraint kind)
     std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
     double *dvar_coef = nullptr; // ... the objective Hessian's coefficients [-s w_0 Q sigma | |x_i,N|^2]
     // ... regularisers that cover a component with a dense triangle at the terminal knot (pcl_host_robust.hpp: var_hess_plan)
@@ -336,6 +337,8 @@ static long long jac_per_full(const pcl_ctx *c) {
     return 2LL * c->cols * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
 static long long jac_per_compact(const pcl_ctx *c) {
+    // a variational context (option var_compact): -B+ | B- | per variation -L+_i | L-_i | tails; exponential: -E | -L_1 .. -L_v | tails
+    if (c->var) return (c->vexp ? 1LL + c->var : 2LL + 2LL * c->var) * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
     if (c->exp) return (long long)c->n * c->n + c->x_dim * (c->desc.n_drives + 1);  // -E | tails (option exp_full)
     return 2LL * c->n * c->n + c->x_dim * (c->desc.n_drives + 1);
 }
@@ -746,7 +749,7 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 }
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    VAR_NOTIMPL(ctx, "pcl_jac_compact_nnz");
+    VAR_COMPACT_GATE(ctx, "pcl_jac_compact_nnz");
     EXP_FULL_GATE(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
     if (nnz) *nnz = jac_per_compact(ctx) * ctx->win_count * ctx->K;
@@ -1494,8 +1497,8 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_eval / pcl_jac")) return rc;
     if (ctx->var) {
-        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (%s)", ctx->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL");
-        return var_launch_fused(ctx, Z, delta, jac);
+        if (compact && !ctx->var_compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (%s)", ctx->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL");
+        return var_launch_fused(ctx, Z, delta, jac, compact && jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
     if (ctx->exp && compact && !ctx->exp_full) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
@@ -2408,10 +2411,20 @@ extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *d
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
-    VAR_NOTIMPL(ctx, "pcl_jac_expand_dev");
+    VAR_COMPACT_GATE(ctx, "pcl_jac_expand_dev");
     EXP_FULL_GATE(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
     const long long n_bk = (long long)ctx->win_count * ctx->K;
+    if (ctx->var) {  // every distinct tile to its cols copies in every segment it occurs in; at one column too (the tiles of component 0 repeat per variation)
+        const int cpi = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_cols_per_slice > 0 ? ctx->opt_cols_per_slice : 3, ctx->cols));
+        const long long tail = (long long)ctx->x_dim * (ctx->desc.n_drives + 1), ntile = ctx->vexp ? 1 + ctx->var : 2 + 2 * ctx->var;
+        const long long grid = n_bk * (ntile * ((ctx->cols + cpi - 1) / cpi) + (tail + 4095) / 4096);
+        if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid);
+        hipLaunchKernelGGL(pcl_var_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, compact, vals, ctx->cols, ctx->n, ctx->desc.n_drives, ctx->var,
+                           ctx->vexp, n_bk, cpi);
+        HIP_TRY(ctx, hipGetLastError());
+        return PCL_OK;
+    }
     if (ctx->exp) {  // [-E | tail] -> [-E x cols | ones | tail], at every column count (one column: the ones are not part of the compact block)
         const int cpi = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_cols_per_slice > 0 ? ctx->opt_cols_per_slice : 3, ctx->cols));
         const long long tail = (long long)ctx->x_dim * (ctx->desc.n_drives + 1);
@@ -2520,8 +2533,8 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const auto t_begin = std::chrono::steady_clock::now();
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
-    // (variational contexts, and exponential ones without the option exp_full: full values, host_path 1)
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->var && (!ctx->exp || ctx->exp_full);
+    // (variational contexts without the option var_compact, and exponential ones without the option exp_full: full values, host_path 1)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -2560,13 +2573,18 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const int cols = ctx->cols;
     const long long nn = (long long)ctx->n * ctx->n, tail = ctx->x_dim * (ctx->desc.n_drives + 1), xd = ctx->x_dim;
     const bool expo = ctx->exp != 0;
+    const int nvar = ctx->var, vexp = ctx->vexp;
     const double *hc = ctx->hcompact;
     int store_w = 0;
     const pcl_host::stream_copy_fn copy = pcl_host::pick_stream_copy((int)ctx->opt_host_store_bytes, &store_w);
     ctx->last_host_store_bytes = store_w;
     ctx->pool->begin(2 * nbk, [=](long long job) {
         const long long bk = job >> 1;
-        if (expo)
+        if (nvar && vexp)
+            pcl_host::expand_interval_var_exp(vals + bk * fper, hc + bk * cper, cols, nn, nvar, xd, tail, (int)(job & 1), copy);
+        else if (nvar)
+            pcl_host::expand_interval_var(vals + bk * fper, hc + bk * cper, cols, nn, nvar, tail, (int)(job & 1), copy);
+        else if (expo)
             pcl_host::expand_interval_exp(vals + bk * fper, hc + bk * cper, cols, nn, xd, tail, (int)(job & 1), copy);
         else
             pcl_host::expand_interval(vals + bk * fper, hc + bk * cper, cols, nn, tail, (int)(job & 1), copy);

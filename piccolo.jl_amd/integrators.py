@@ -71,14 +71,23 @@ def _check_exp_full(exp_full, pade_order, batch_mode=PCL_BATCH_MEMBERS):
         raise ValueError("exp_full=True is not served on a variational context")
 
 
+def _check_var_compact(var_compact, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``var_compact`` (the library's option of that name) belongs to a variational context, of either constraint kind: on any other
+    one it is a ``ValueError``, before any device call."""
+    if var_compact and batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("var_compact=True serves the compact Jacobian of a variational context (VariationalUnitaryIntegrator / "
+                         "VariationalKetIntegrator): a plain context has its compact Jacobian without it")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
-                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False):  # fmt: skip
+                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False):  # fmt: skip
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order, batch_mode)
+        _check_var_compact(var_compact, batch_mode)
         if exp_hessian and pade_order != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
         if exp_hessian == "workspace" and batch_mode != PCL_BATCH_VARIATIONAL_EXP:
@@ -120,6 +129,7 @@ class _PclContext:
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         self.exp_hessian = False  # (follows the library's option: set_option keeps it and hess_nnz / hess_per current)
         self.exp_full = False  # (the same: set_option keeps it and compact_nnz / compact_per current)
+        self.var_compact = False  # (the same on a variational context, of either constraint kind)
         self.hess_nnz = self.hess_per = 0
         self.compact_nnz = self.compact_per = 0
         if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
@@ -133,7 +143,9 @@ class _PclContext:
             self.hess_nnz, self.hess_per = a.value, b.value
         if exp_full:
             self.set_option("exp_full", 1)
-        # (no compact Jacobian for the stacked state; the exponential constraint's by ``exp_full`` only: set_option has the sizes)
+        if var_compact:
+            self.set_option("var_compact", 1)
+        # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
         if batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) and not self.exponential:
             self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
             self.compact_nnz, self.compact_per = a.value, b.value
@@ -451,6 +463,12 @@ class _PclContext:
             if self.exp_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
+        if key == "var_compact" and self.batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):  # ... the stacked state's compact Jacobian
+            self.var_compact = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.var_compact:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.compact_nnz, self.compact_per = a.value, b.value
         if self.exponential and key == "exp_full":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
             self.exp_full = bool(value)
             a, b = ctypes.c_int64(), ctypes.c_int64()
@@ -513,7 +531,7 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False):
+                 exp_full=False, var_compact=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -524,9 +542,11 @@ class HipPadeIntegrator:
         ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served too
         (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62.
         ``exp_full=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the compact Jacobian, the host-pointer calls' compact path and the
-        merit / reduce payload are served on that constraint too (the library's option ``exp_full``)."""
+        merit / reduce payload are served on that constraint too (the library's option ``exp_full``).
+        ``var_compact`` belongs to the variational constructors: ``True`` here is a ``ValueError``."""
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order)
+        _check_var_compact(var_compact)
         if exp_hessian == "workspace":
             raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint: a plain integrator takes False or True")
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
@@ -622,9 +642,14 @@ class HipVariationalIntegrator:
     the library's option ``var_exp_hess`` on: the Hessian of the Lagrangian of that constraint is then served too, for generator dimensions up
     to 44 (nine LDS tiles; beyond that the constructor raises the library's PCL_ESHAPE message).  ``exp_hessian="workspace"`` sets the option
     ``var_exp_hess_tiles`` = 1 first: where nine tiles exceed the LDS (generator dimensions 46 .. 62, config 3 among them) four of them live in
-    a device workspace, elsewhere nothing changes.  Any other value is a ``ValueError``.  It is never on by itself."""
+    a device workspace, elsewhere nothing changes.  Any other value is a ``ValueError``.  It is never on by itself.
 
-    def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False):
+    ``var_compact=True`` (any Pade order, or ``"exp"``) switches the library's option ``var_compact`` on: the compact Jacobian of the stacked
+    state -- every distinct tile once, ``ctx.compact_per`` values per interval -- its device expansion, and the host-pointer calls' compact
+    path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
+
+    def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
+                 var_compact=False):
         exp_hessian = _exp_hessian_value(exp_hessian)
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
@@ -659,7 +684,7 @@ class HipVariationalIntegrator:
             d=sys.levels, m=m, N=traj.N, z_dim=traj.dim, u_off=traj.components[u_name].start, dt_off=traj.components[traj.timestep].start,
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
             batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
-            index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian,
+            index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
@@ -724,7 +749,7 @@ def _variational_generators(sys, scales):
 def VariationalUnitaryIntegrator(sys, traj, x_name, x_variations, u_name="u", *, scales=None, **kw):
     """``VariationalUnitaryIntegrator(sys, traj, :U, [:U_var, ...], :u; scales)`` [REF src/control/integrators.jl:247-264]: generator
     ``var_G(I (x) G(u), [I (x) G_var_i / scales[i]])`` on ``vcat(U, U_var_1, ...)``; ``scales`` defaults to ones.  Keyword arguments as for
-    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``, ``exp_hessian``: ``False`` | ``True`` | ``"workspace"``)."""
+    ``HipPadeIntegrator`` (``pade_order``, ``order_tol``, ``device``, ``index_base``, ``exp_hessian``: ``False`` | ``True`` | ``"workspace"``, ``var_compact``)."""
     Gv = _variational_generators(sys, 1.0 if scales is None else scales)
     return HipVariationalIntegrator(sys, traj, x_name, x_variations, u_name, Gv, ket=False, **kw)
 

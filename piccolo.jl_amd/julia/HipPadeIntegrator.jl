@@ -275,9 +275,13 @@ end
 #      pade_order = :exp only) switches the library's option var_exp_hess on BEFORE the Hessian structure is queried -- generator
 #      dimensions up to 44; never on by itself.  exp_hessian = :workspace sets the option var_exp_hess_tiles = 1 first: where nine LDS tiles do
 #      not fit (generator dimensions 46 .. 62, config 3 among them) four of them live in a device workspace.  Any other value: ArgumentError.
-#      (This keyword's glue has not been executed: no Julia on the development machines.)
+#      var_compact = true (any order, or :exp): the library's option var_compact -- pcl_eval_jac / pcl_jac then deliver the Jacobian values
+#      through the compact ones (every distinct tile once over PCIe, replicated by the host's threads) where the blocks are replicated;
+#      off by default, never on by itself.
+#      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
-                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false)
+                      device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
+                      var_compact::Bool = false)
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
     (exp_hessian isa Symbol && exp_hessian != :workspace) &&
@@ -310,6 +314,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     check(c, ccall((:pcl_jac_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     workspace && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess_tiles", 1))
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
+    var_compact && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_compact", 1))
     (expo && !exp_hessian) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
