@@ -195,6 +195,30 @@ typedef enum pcl_status {
                                effect.  get_option "pade_order" reads -1, "variations" v, "last_kernel" 110 (residual + Jacobian) or 111
                                (residual only). */
 
+/* pcl_desc.batch_mode flag, OR-ed with PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ: generator dimensions 66 .. 128 on the Pade constraint -- the
+ * reference's transmon-cavity template (4 x 12 levels: n = 96; 4 x 15: n = 120), compact density vectors of 9 .. 11 levels (n = 81, 100, 121),
+ * cat-buffer systems, ion chains with phonon modes.  Chosen at creation only; nothing sets it on its own, and without it every context is what
+ * it was (n > 64: PCL_ESHAPE).  pcl_create strips the flag and stores the plain batch mode.  With the flag:
+ *   n <= 64                the ordinary context: the same kernels, the same bits
+ *   66 <= n <= 128         a LARGE context; even n for unitary / ket / multi-ket states, any n (odd included) under PCL_STATE_VECTOR
+ *   n > 128                PCL_ESHAPE (one n x n LDS tile is all a workgroup's 163,840 B can hold: 132,096 B at n = 128)
+ *   PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP or pade_order = PCL_ORDER_EXP: PCL_ENOTIMPL
+ * -- all decided before the device is touched.  A large context runs one kernel family (pcl_kernel_pade_large.hpp: one LDS tile, the powers of
+ * G by column panels, the drives in groups where their chain blocks do not fit beside the tile) at Pade orders 2 .. 10 with
+ * shared or per-member G0, both batch modes, the member window, 1 .. d state columns and m = 0 .. 24 drives; values, order and layout are those
+ * of every other Pade context.  Every work split gives the same bits and two launches give the same bits (no atomics).
+ * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
+ * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, and pade_order = 0 with
+ * pcl_set_order_policy / pcl_set_order_from_trajectory.  PCL_ENOTIMPL, each message naming PCL_LARGE_N: pcl_hess[_dev], pcl_hess_nnz,
+ * pcl_hess_structure[_i64] (solve with a quasi-Newton Hessian, the reference's eval_hessian = false), the compact Jacobian trio, the merit /
+ * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev), pcl_rollout[_dev] and
+ * the objective family (goals, weights, regularisers, pcl_infidelity_dev, pcl_objective[_dev], pcl_objective_hess_*).
+ * Options: "cols_per_slice" caps the state columns per workgroup, "general_slices" sets the least number of workgroups per interval;
+ * "kernel_version", "general_kernel_version", "general_threads", "use_mfma", "nt" = 2 have no effect.  get_option "last_kernel" reads 290 + q
+ * after a Jacobian launch and 280 + q after a residual-only launch (q = pade_order / 2). */
+#define PCL_LARGE_N 0x100
+#define PCL_LARGE_MAX_N 128
+
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
     int32_t d;           /* Hilbert-space dimension (sys.levels); n = 2d, x_dim = 2 d^2 */

@@ -141,6 +141,7 @@ static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int
     return set_form(ctx, 0, R, A.data(), nullptr, false);
 }
 extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c) {
+    LARGE_NOTIMPL(ctx, "pcl_set_goal_form");
     VAR_GATE(ctx, "pcl_set_goal_form");
     if (ctx && ctx->var) return var_set_goal_form(ctx, scope, R, A, c);
     if (!ctx) return PCL_EINVAL;
@@ -155,6 +156,7 @@ extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const d
     return set_form(ctx, scope, R, A, c, true);
 }
 extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
+    LARGE_NOTIMPL(ctx, "pcl_set_goal");
     VAR_GATE(ctx, "pcl_set_goal");
     if (ctx && ctx->var) return var_set_goal(ctx, goal_iso_vec);
     if (!ctx) return PCL_EINVAL;
@@ -171,6 +173,7 @@ extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
     return unitary_form(ctx, goal_iso_vec);
 }
 extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns) {
+    LARGE_NOTIMPL(ctx, "pcl_set_goal_subspace");
     VAR_GATE(ctx, "pcl_set_goal_subspace");
     if (ctx && ctx->var) return var_set_goal_subspace(ctx, goal_sub_iso_vec, subspace, ns);
     if (!ctx) return PCL_EINVAL;
@@ -198,6 +201,7 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
 }
 extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
+    LARGE_NOTIMPL(ctx, "pcl_set_weights");
     VAR_GATE(ctx, "pcl_set_weights");
     if (ctx && ctx->var) return var_set_weights(ctx, w);
     if (!ctx) return PCL_EINVAL;
@@ -214,6 +218,7 @@ extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
     return PCL_OK;
 }
 extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const double *R, int32_t dt_power) {
+    LARGE_NOTIMPL(ctx, "pcl_add_regularizer");
     VAR_GATE(ctx, "pcl_add_regularizer");
     if (!ctx) return PCL_EINVAL;
     if (!R || dim < 1 || off < 0 || off + dim > ctx->desc.z_dim) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: component [%d, %d) outside the knot (z_dim=%d)", off, off + dim, ctx->desc.z_dim);
@@ -226,6 +231,7 @@ extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const
     return PCL_OK;
 }
 extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
+    LARGE_NOTIMPL(ctx, "pcl_clear_regularizers");
     VAR_GATE(ctx, "pcl_clear_regularizers");
     if (!ctx) return PCL_EINVAL;
     ctx->regs.clear();
@@ -235,6 +241,7 @@ extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
 }
 static unsigned infidelity_lds(const pcl_ctx *ctx) { return (unsigned)(6 * (size_t)ctx->n_sub * ctx->n_sub * sizeof(double)); }
 extern "C" int pcl_infidelity_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    LARGE_NOTIMPL(ctx, "pcl_infidelity_dev");
     VAR_NOTIMPL(ctx, "pcl_infidelity_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || (!value && !grad)) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: NULL pointer");
@@ -282,6 +289,7 @@ static int objective_prepare(pcl_ctx *ctx) {
 static bool tail_applies(const pcl_ctx *ctx, const double *grad, int &lo_, int &hi_);
 static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad, int skip_lo, int skip_hi, double *merit_out);
 extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    LARGE_NOTIMPL(ctx, "pcl_objective_dev");
     VAR_GATE(ctx, "pcl_objective_dev");
     if (ctx && ctx->var) return var_objective_dev(ctx, Z, Q, value, grad);
     if (!ctx) return PCL_EINVAL;
@@ -340,6 +348,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
     return PCL_OK;
 }
 extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
+    LARGE_NOTIMPL(ctx, "pcl_objective");
     VAR_GATE(ctx, "pcl_objective");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective: NULL pointer");
@@ -410,6 +419,7 @@ static int launch_exp_merit(pcl_ctx *ctx, const double *Z, const double *lam, do
 }
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
+    LARGE_NOTIMPL(ctx, "pcl_merit_grad_dev");
     VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
     EXP_FULL_GATE(ctx, "pcl_merit_grad_dev");
     if (!ctx) return PCL_EINVAL;
@@ -427,6 +437,7 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 }
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
+    LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
     if (ctx && ctx->exp && !ctx->exp_full && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_dev");
@@ -485,6 +496,7 @@ static long long obj_hess_per_knot(const pcl_ctx *ctx) {
     return n;
 }
 extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
+    LARGE_NOTIMPL(ctx, "pcl_objective_hess_nnz");
     VAR_GATE(ctx, "pcl_objective_hess_nnz");
     if (ctx && ctx->var) return var_objective_hess_nnz(ctx, nnz);
     if (!ctx || !nnz) return PCL_EINVAL;
@@ -493,6 +505,7 @@ extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols) {
+    LARGE_NOTIMPL(ctx, "pcl_objective_hess_structure");
     VAR_GATE(ctx, "pcl_objective_hess_structure");
     if (ctx && ctx->var) return var_objective_hess_structure(ctx, rows, cols);
     if (!ctx || !rows || !cols) return PCL_EINVAL;
@@ -527,6 +540,7 @@ extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, i
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
+    LARGE_NOTIMPL(ctx, "pcl_objective_hess_dev");
     VAR_GATE(ctx, "pcl_objective_hess_dev");
     if (ctx && ctx->var) return var_objective_hess_dev(ctx, Z, Q, sigma, vals);
     if (!ctx) return PCL_EINVAL;
@@ -562,6 +576,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
+    LARGE_NOTIMPL(ctx, "pcl_objective_hess");
     VAR_GATE(ctx, "pcl_objective_hess");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess: NULL pointer");
@@ -655,6 +670,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 // regulariser rows, the terminal infidelities and the payload's finish (pcl_ens_tail_kernel); the same bits as the separate calls.
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
+    LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;
@@ -685,6 +701,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
     return PCL_OK;
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
+    LARGE_NOTIMPL(ctx, "pcl_merit_grad_len");
     VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
     EXP_FULL_GATE(ctx, "pcl_merit_grad_len");
     if (!ctx) return PCL_EINVAL;

@@ -1,0 +1,233 @@
+// Large-generator kernel (contexts created with PCL_LARGE_N, 66 <= n <= 128): residual, and residual + Jacobian, for the diagonal Pade orders
+// p = 2q (q <= 5).  Outputs, value order and layout are those of pcl_pade_kernel<JAC> (pcl_kernels_reference.hpp) for the same KParams.
+//
+// The formulation is the lock-step one of pcl_kernel_pade_v2.hpp -- per level ONE product  G [W | V | dW_l .. | P]  on the matrix cores, the
+// three Horner recursions and the panel of the powers of G side by side -- with the fixed counts of n <= 64 taken out:
+//   - ONE n x n tile in LDS (LD = n | 1: 132,096 B at n = 128) and what is left of the 163,840 B in column blocks of LD doubles (29 at n = 128);
+//   - one wave per 16-row tile of G (blockDim = 64 ceil(n / 16): 5 .. 8 waves, at most 2 per SIMD, so 256 registers per lane): the wave's
+//     A operand, 32 k-steps, stays in registers over all levels (64 registers); the B operand is read 16 k-steps at a time;
+//   - an interval is split into U units, one workgroup each.  Unit u < sx ngrp is a CHAIN unit: state-column slice s = u % sx (nc columns)
+//     and drive group g = u / sx (mg drives): it runs W, V and the dW_l of its drives (W is needed by every group and is formed by each
+//     with the same operations, hence the same bits).  Group 0 stores delta and the dt tail, every group the tails of its drives.  Every
+//     unit u with u npc < n also carries the PANEL of columns [u npc, (u + 1) npc) of the powers of G, accumulates that panel of B^{+-} in
+//     registers (PL_NP pairs per thread) and writes it to all `cols` copies;
+//   - odd n (PCL_STATE_VECTOR): LD = n, so the panel is contiguous in LDS as it is in memory and a thread's pair may straddle two columns;
+//     the block stores are then scalar (the blocks are not 16-byte aligned).
+// LDS (doubles): G | -S | D | X (T nc) | X' (T nc) | P' (npc) | slack | us      T = 2 + mg blocks per state column (JAC), 1 (residual only).
+// After the A operands are in registers nothing reads G as a matrix again: the panel rotates between P' and its own columns of G.
+// Every element of every output is formed by one fixed sequence of operations whatever the split (sx, mg, npc): the k order of the products
+// is fixed, the additive terms are explicit fused multiply-adds, and no sum crosses a unit -- no atomics, and every split gives the same bits.
+// The drives' ELL rows are read from memory (L2): at m = 24, n = 120 they are 69 KB.
+#pragma once
+
+#define PL_KS 32     // k-steps of 4 (n <= 128)
+#define PL_NT 512    // most threads per workgroup (8 row tiles)
+#define PL_NP 8      // B^{+-} value pairs per thread (the host keeps n npc / 2 <= PL_NP blockDim)
+#define PL_SLACK 128 // doubles behind the last column block: the B operand loads of a column run 128 rows whatever n is
+
+// one 16 x 16 tile of G * B: a[] = this wave's rows of G, Bp = this lane's column of B in LDS + (lane >> 4), kmask = the k-steps with a nonzero
+// in the wave's rows (wave-uniform).  Operand loads are unconditional, base + immediate: every double of the workgroup's LDS is finite
+// (zero-filled at the start), and where k >= n the A operand is an exact zero
+__device__ __forceinline__ double4_t pl_tile(const double (&a)[PL_KS], const double *__restrict__ Bp, unsigned kmask) {
+    // k-step ks into accumulator ks mod 4: four independent chains (a dependent f64 MFMA waits for its accumulator), summed in one fixed order
+    double4_t acc[4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        double b[PL_KS / 2];
+#pragma unroll
+        for (int ks = 0; ks < PL_KS / 2; ++ks) b[ks] = Bp[4 * (ks + half * (PL_KS / 2))];
+#pragma unroll
+        for (int ks = 0; ks < PL_KS / 2; ++ks)
+            if (kmask & (1u << (ks + half * (PL_KS / 2))))
+                acc[ks & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks + half * (PL_KS / 2)], b[ks], acc[ks & 3], 0, 0, 0);
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
+// p.S = U units per interval, p.nc state columns per chain unit; sx state-column slices, mg drives per group, npc power columns per unit
+template <bool JAC>
+__global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, const int sx, const int mg, const int npc) {
+    extern __shared__ double lds[];
+    const int n = p.n, d = p.cols, m = p.m, LD = p.LD, nc = p.nc, q = p.q, U = p.S;
+    const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, rt = tid >> 6;  // one wave per row tile
+    const int li = lane & 15, lk = lane >> 4;
+    const long long bid = blockIdx.x;
+    const long long item = bid / U;
+    const int u = (int)(bid % U);
+    const int k = (int)(item % p.K), b = (int)(item / p.K);
+    const double *zk = p.Z + (long long)b * p.z_batch_stride + (long long)k * p.z_dim;
+    const double *zn = zk + p.z_dim;
+    const double h = zk[p.dt_off];
+    const long long nn = (long long)n * n;
+    const int ngrp = (JAC && m > 0) ? (m + mg - 1) / mg : 1;
+    const bool chain = u < sx * ngrp;
+    const int s = chain ? u % sx : 0, g = chain ? u / sx : 0;
+    const int c0 = s * nc, nce = chain ? max(0, min(nc, d - c0)) : 0;           // this unit's state columns
+    const int l0 = g * mg, mge = (JAC && chain) ? max(0, min(mg, m - l0)) : 0;  // ... and drives
+    const int T = JAC ? 2 + mg : 1, LDc = LD * nc;
+    const int pc0 = JAC ? u * npc : n, npce = max(0, min(npc, n - pc0));        // ... and columns of the powers
+    double *G = lds;
+    double *Sm = G + LD * n, *Dm = Sm + LDc, *Xc = Dm + LDc, *Xn = Xc + T * LDc;  // X: W | V | dW_l0 .. (JAC), W alone otherwise
+    double *Pn = Xn + T * LDc, *Pc = G + LD * (npce > 0 ? pc0 : 0);
+    double *us = Pn + (JAC ? LD * npc : 0) + PL_SLACK;
+    for (int e = tid; e < p.lds_doubles; e += nth) lds[e] = 0.0;
+    __syncthreads();
+    const int x_off = p.x_offs[p.z_batch_stride ? 0 : b];
+    build_G(p, p.G0 + (long long)b * p.g0_batch_stride, zk, G, us);
+    const double cq = p.pc[q];
+    for (int e = tid; e < nce * n; e += nth) {  // (columns beyond nce and the dW blocks stay zero)
+        const int c = e / n, i = e - c * n;
+        const double xn = zn[x_off + (c0 + c) * n + i], xc = zk[x_off + (c0 + c) * n + i];
+        const double xs = xn + xc, xdv = xn - xc;
+        const int idx = i + LD * c;
+        Sm[idx] = -xs;
+        Dm[idx] = xdv;
+        const double yq = (q & 1) ? -xs : xdv;
+        Xc[idx] = cq * yq;
+        if (JAC) Xc[LDc + idx] = (q * cq) * yq;
+    }
+    __syncthreads();
+    double a[PL_KS];
+#pragma unroll
+    for (int ks = 0; ks < PL_KS; ++ks) {
+        const int row = rt * 16 + li, kk = 4 * ks + lk;
+        a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
+    }
+    // 16 x 4 blocks of G without a nonzero are skipped (a dispersive qubit-cavity generator has a handful per row tile): adding their
+    // exact-zero products changes nothing but the sign of a zero sum.  The mask depends on G alone, never on the split
+    unsigned kmask = 0;
+#pragma unroll
+    for (int ks = 0; ks < PL_KS; ++ks)
+        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
+    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    // B^{+-}: each thread owns the flat positions (2 pi, 2 pi + 1), pi = tid + nth r, of the unit's panel (n x npce, contiguous in memory;
+    // in LDS too when n is odd, LD = n; for an even n both positions lie in one column); first terms I + c_1 (+-h) G
+    double bp[PL_NP][2], bm[PL_NP][2];
+    int o_[PL_NP];
+    double hp = h, hm = -h;
+    const int ptot = n * npce;
+    if (JAC) {
+#pragma unroll
+        for (int r = 0; r < PL_NP; ++r) {
+            const int pos = 2 * (tid + nth * r);
+            o_[r] = -1;
+            bp[r][0] = bm[r][0] = bp[r][1] = bm[r][1] = 0.0;
+            if (pos < ptot) {
+                const int c = pos / n, i = pos - c * n, c1 = (pos + 1) / n, i1 = pos + 1 - c1 * n;
+                o_[r] = i + LD * c;
+                bp[r][0] = bm[r][0] = (i == pc0 + c) ? 1.0 : 0.0;
+                bp[r][1] = bm[r][1] = (i1 == pc0 + c1) ? 1.0 : 0.0;
+                const double v0 = Pc[o_[r]], v1 = Pc[o_[r] + 1];  // (the last position of an odd panel has no partner: finite padding, never stored)
+                bp[r][0] += p.pc[1] * hp * v0;
+                bp[r][1] += p.pc[1] * hp * v1;
+                bm[r][0] += p.pc[1] * hm * v0;
+                bm[r][1] += p.pc[1] * hm * v1;
+            }
+        }
+    }
+    const int cx = chain ? T * nc : 0, ct_n = (cx + (JAC ? npc : 0) + 15) >> 4;
+    const int ew = p.ell_w;
+    for (int j = q - 1; j >= 0; --j) {
+        const double *Yj = (j & 1) ? Sm : Dm;
+        const double cj = p.pc[j];
+        for (int ct = 0; ct < ct_n; ++ct) {
+            if (j == 0 && ct * 16 >= cx) break;  // the last level forms no power
+            const int vc = ct * 16 + li;
+            const bool isp = vc >= cx;  // a column of the powers
+            const int bl = isp ? T : vc / nc, c = isp ? vc - cx : vc - bl * nc;
+            const bool on = isp ? (j > 0 && c < npce) : (c < nce && (bl < 2 || bl - 2 < mge));
+            const double4_t acc = pl_tile(a, (on ? (isp ? Pc : Xc + bl * LDc) + LD * c : G) + lk, kmask);
+            if (on) {
+                // the additive term of each element: c_j Y_j, j c_j Y_j, or the drive's sparse product with the old W.  Loads are unconditional
+                // (rows beyond n - 1 read finite padding; the stores below are predicated)
+                const int r0 = rt * 16 + lk;
+                double y[4] = {0.0, 0.0, 0.0, 0.0};
+                if (bl <= 1) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) y[r] = Yj[r0 + 4 * r + LD * c];
+                } else if (!isp) {
+                    const double *wc = Xc + LD * c;
+                    const long long lrow = (long long)(l0 + bl - 2) * n;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * ew;
+                        double v = 0.0;
+                        for (int e = 0; e < ew; ++e) v = __builtin_fma(p.ell_val[eb + e], wc[p.ell_col[eb + e]], v);
+                        y[r] = v;
+                    }
+                }
+                double *dst = (isp ? Pn : Xn + bl * LDc) + LD * c;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int rr = r0 + 4 * r;
+                    double o;
+                    if (bl == 0)
+                        o = __builtin_fma(h, acc[r], cj * y[r]);
+                    else if (bl == 1)
+                        o = j ? __builtin_fma(h, acc[r], (j * cj) * y[r]) : acc[r];
+                    else if (!isp)
+                        o = h * (acc[r] + y[r]);
+                    else
+                        o = acc[r];
+                    if (rr < n) dst[rr] = o;
+                }
+            }
+        }
+        __syncthreads();  // level j is complete in X' / P'; nothing reads X / P any more
+        double *t_ = Xc;
+        Xc = Xn;
+        Xn = t_;
+        if (JAC && j > 0) {  // the next power: its term of B^{+-}
+            t_ = Pc;
+            Pc = Pn;
+            Pn = t_;
+            const int pw = q + 1 - j;
+            hp *= h;
+            hm *= -h;
+#pragma unroll
+            for (int r = 0; r < PL_NP; ++r)
+                if (o_[r] >= 0) {
+                    const double v0 = Pc[o_[r]], v1 = Pc[o_[r] + 1];
+                    bp[r][0] += p.pc[pw] * hp * v0;
+                    bp[r][1] += p.pc[pw] * hp * v1;
+                    bm[r][0] += p.pc[pw] * hm * v0;
+                    bm[r][1] += p.pc[pw] * hm * v1;
+                }
+        }
+    }
+    const long long xd = (long long)n * d;
+    if (p.delta && g == 0)
+        for (int e = tid; e < nce * n; e += nth) p.delta[item * xd + (long long)c0 * n + e] = Xc[(e % n) + LD * (e / n)];
+    if (!JAC) return;
+    double *jb = p.jac + item * p.jac_per;
+    const long long blk = (long long)d * nn;
+    // tails [c][l | dt][i]: this group's drives, and the dt block from group 0
+    const int nl = mge + (g == 0 ? 1 : 0);
+    double *jt = jb + 2 * blk;
+    for (int e = tid; e < nl * nce * n; e += nth) {
+        const int i = e % n, t = (e / n) % nl, c = e / (n * nl);
+        const int l = t < mge ? l0 + t : m;
+        jt[((long long)(c0 + c) * (m + 1) + l) * n + i] = Xc[(t < mge ? 2 + t : 1) * LDc + i + LD * c];
+    }
+    // -B^+ and B^-: this unit's panel, into every replicated position
+    const bool even = !(n & 1);
+#pragma unroll
+    for (int r = 0; r < PL_NP; ++r)
+        if (o_[r] >= 0) {
+            const int pos = 2 * (tid + nth * r);
+            double *o0 = jb + (long long)pc0 * n + pos;
+            for (int c = 0; c < d; ++c) {
+                if (even) {
+                    store2(o0 + c * nn, -bp[r][0], -bp[r][1], p.nt);
+                    store2(o0 + blk + c * nn, bm[r][0], bm[r][1], p.nt);
+                } else {
+                    o0[c * nn] = -bp[r][0];
+                    o0[blk + c * nn] = bm[r][0];
+                    if (pos + 1 < ptot) {
+                        o0[c * nn + 1] = -bp[r][1];
+                        o0[blk + c * nn + 1] = bm[r][1];
+                    }
+                }
+            }
+        }
+}

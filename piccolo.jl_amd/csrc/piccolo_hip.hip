@@ -5,6 +5,7 @@
 //   pcl_kernels_fused_v2.hpp   fallback (two workgroups per CU); also kets and the compact Jacobian at large n
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
+//   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
 //   pcl_kernels_hessian.hpp    Hessian of the Lagrangian: versions 1 (one workgroup per interval) and 2 (column chunks, fallback)
 //   pcl_kernel_hessian_v3.hpp  Hessian of the Lagrangian, default: one workgroup per interval, jobs split by drive
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
@@ -43,6 +44,7 @@
 #include "pcl_device_common.hpp"
 #include "pcl_kernels_reference.hpp"
 #include "pcl_kernel_pade_v2.hpp"
+#include "pcl_kernel_pade_large.hpp"
 #include "pcl_kernels_fused_v2.hpp"
 #include "pcl_kernel_fused_v3.hpp"
 #include "pcl_kernel_eval.hpp"
@@ -66,6 +68,7 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
+    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); Hessian, compact Jacobian, merit / reduce, rollout and objective are refused
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
     int exp_full = 0;            // ... option exp_full: the compact Jacobian trio, the host expansion and the merit / reduce payload are served
@@ -375,6 +378,13 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
         if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
     } while (0)
 
+// A large context (PCL_LARGE_N, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is refused in these words.
+#define LARGE_NOTIMPL(ctx, what)                                                                                                                          \
+    do {                                                                                                                                                  \
+        if ((ctx) && (ctx)->large)                                                                                                                        \
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
+    } while (0)
+
 #define EXP_HESS_GATE(ctx, what)                       \
     do {                                               \
         if ((ctx) && !(ctx)->exp_hess) EXP_NOTIMPL(ctx, what); \
@@ -392,6 +402,18 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
+    // PCL_LARGE_N: stripped here, once; everything below (and the context) sees the plain batch mode
+    const bool large_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_N) != 0;
+    pcl_desc plain_desc = *dsc;
+    if (large_flag) {
+        plain_desc.batch_mode &= ~PCL_LARGE_N;
+        dsc = &plain_desc;
+        if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP)
+            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the variational integrators (batch_mode %s); it goes with PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ",
+                        dsc->batch_mode == PCL_BATCH_VARIATIONAL ? "PCL_BATCH_VARIATIONAL" : "PCL_BATCH_VARIATIONAL_EXP");
+        if (dsc->pade_order == PCL_ORDER_EXP)
+            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the exponential constraint (pade_order = PCL_ORDER_EXP); it serves the diagonal Pade orders 2 .. 10");
+    }
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL && dsc->pade_order == PCL_ORDER_EXP)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented; use batch_mode = PCL_BATCH_VARIATIONAL_EXP");
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP) return var_create(dsc, out);
@@ -400,8 +422,13 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (d < 1 || m < 0 || dsc->N < 2 || dsc->batch < 1)
         return fail(nullptr, PCL_EINVAL, "pcl_create: need d>=1, n_drives>=0, N>=2, batch>=1 (got d=%d m=%d N=%d batch=%d)", d,
                     m, dsc->N, dsc->batch);
-    if (n > 2 * PCL_MAX_D)
-        return fail(nullptr, PCL_ESHAPE, "pcl_create: generator dimension %d exceeds %d (LDS-resident tiles; d <= %d)", n, 2 * PCL_MAX_D, PCL_MAX_D);
+    if (n > 2 * PCL_MAX_D && !large_flag)
+        return fail(nullptr, PCL_ESHAPE, "pcl_create: generator dimension %d exceeds %d (LDS-resident tiles; d <= %d); batch_mode | PCL_LARGE_N serves the Pade constraint up to %d", n, 2 * PCL_MAX_D,
+                    PCL_MAX_D, PCL_LARGE_MAX_N);
+    if (n > PCL_LARGE_MAX_N)
+        return fail(nullptr, PCL_ESHAPE, "pcl_create: generator dimension %d exceeds %d, the most PCL_LARGE_N serves: one n x n LDS tile would take %zu B of the 163840 B a workgroup can have (132096 B at n = %d)",
+                    n, PCL_LARGE_MAX_N, (size_t)(n | 1) * n * sizeof(double), PCL_LARGE_MAX_N);
+    const bool large = large_flag && n > 2 * PCL_MAX_D;  // (the flag at n <= 64: the ordinary context)
     if (m > 24) return fail(nullptr, PCL_ESHAPE, "pcl_create: n_drives=%d exceeds 24", m);
     if (dsc->pade_order < PCL_ORDER_EXP)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order=%d; accepted values are the diagonal Pade orders 2, 4, 6, 8, 10, 0 (chosen by pcl_set_order_policy) and PCL_ORDER_EXP (-1, the exponential constraint)", dsc->pade_order);
@@ -437,6 +464,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     ctx->x_dim = x_dim;
     ctx->cols = cols;
     ctx->vec = vec ? 1 : 0;
+    ctx->large = large ? 1 : 0;
     ctx->exp = dsc->pade_order == PCL_ORDER_EXP ? 1 : 0;
     ctx->x_offs.assign(dsc->x_offs, dsc->x_offs + n_off);
     ctx->hG0.assign(dsc->G0, dsc->G0 + (size_t)n * n * (dsc->per_member_G0 ? dsc->batch : 1));
@@ -749,6 +777,7 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 }
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
+    LARGE_NOTIMPL(ctx, "pcl_jac_compact_nnz");
     VAR_COMPACT_GATE(ctx, "pcl_jac_compact_nnz");
     EXP_FULL_GATE(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
@@ -757,6 +786,7 @@ extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *pe
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
+    LARGE_NOTIMPL(ctx, "pcl_hess_nnz");
     VAR_EXP_NOHESS(ctx, "pcl_hess_nnz");
     EXP_HESS_GATE(ctx, "pcl_hess_nnz");
     if (per) *per = hess_per(ctx);
@@ -827,6 +857,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
+    LARGE_NOTIMPL(ctx, "pcl_hess_structure");
     VAR_EXP_NOHESS(ctx, "pcl_hess_structure");
     EXP_HESS_GATE(ctx, "pcl_hess_structure");
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
@@ -1134,6 +1165,83 @@ static int launch_pade_v2(pcl_ctx *ctx, KParams &p) {
     hipLaunchKernelGGL(pcl_pade_v2_kernel, dim3((unsigned)grid), dim3(PV2_NT), lds, ctx->stream, p);
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_kernel = 190 + p.q;
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
+static void fill_pade(KParams &p, int order);
+// Large-generator kernel (pcl_kernel_pade_large.hpp; contexts created with PCL_LARGE_N).  The plan: LD = n | 1, 64 threads per 16-row tile of G;
+// what the one tile leaves of the LDS is NB column blocks of LD doubles.  A chain unit takes nc state columns and mg drives:
+// nc (2 + 2 (2 + mg)) blocks (-S, D, and W | V | dW_l twice) with the Jacobian, 4 nc (W alone) without.  The widest nc that leaves room for
+// one drive and one power column is taken (option cols_per_slice caps it) and evened over the slices, then the most drives per group that fit,
+// evened over the groups;
+// then units are added until the panel of ceil(n / U) power columns fits beside the chain blocks and a thread owns at most PL_NP pairs of it,
+// and, for launches of few intervals, up to one unit per 16 power columns while the grid stays within one round of the CUs (option
+// general_slices: that many units at least).  Every split gives the same bits.
+struct LargePlan {
+    int LD, threads, NB, sx, nc, mg, ngrp, U, npc;
+    size_t lds;
+};
+static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargePlan &P) {
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
+    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
+    P.nc = 1, P.mg = jac && m > 0 ? 1 : 0;
+    for (int nc = nc_cap; nc >= 1; --nc) {
+        if (!jac) {
+            if (4 * nc > P.NB && nc > 1) continue;
+            P.nc = nc;
+            break;
+        }
+        const int mg_max = m > 0 ? std::min(m, ((P.NB - 1) / nc - 6) / 2) : 0;
+        if ((m > 0 ? mg_max < 1 : 6 * nc + 1 > P.NB) && nc > 1) continue;
+        P.nc = nc;
+        P.mg = m > 0 ? std::max(mg_max, 1) : 0;
+        break;
+    }
+    P.ngrp = jac && m > 0 ? (m + P.mg - 1) / P.mg : 1;
+    if (jac && m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
+    P.sx = (cols + P.nc - 1) / P.nc;
+    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    const int chain_units = P.sx * P.ngrp, chain_blocks = P.nc * (jac ? 2 + 2 * (2 + P.mg) : 4);
+    P.U = chain_units;
+    P.npc = 0;
+    if (jac) {
+        auto fits = [&](int U) {
+            const int npc = (n + U - 1) / U;
+            return chain_blocks + npc <= P.NB && ((long long)n * npc + 1) / 2 <= (long long)PL_NP * P.threads;
+        };
+        while (P.U < n && !fits(P.U)) ++P.U;
+        const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices
+                                                          : std::min<long long>(std::max(chain_units, (n + 15) / 16), ctx->n_cu / std::max(items, 1LL));
+        P.U = (int)std::max<long long>(P.U, std::min<long long>(want, n));
+        P.npc = (n + P.U - 1) / P.U;
+        P.U = std::max(chain_units, (n + P.npc - 1) / P.npc);  // (no unit without work)
+    }
+    P.lds = (size_t)(fixed + (long long)P.LD * (chain_blocks + P.npc)) * sizeof(double);
+}
+static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac) {
+    fill_pade(p, ctx->desc.pade_order);
+    LargePlan P;
+    const long long items = (long long)p.batch * p.K;
+    large_plan(ctx, p.n, p.cols, p.m, want_jac, items, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large-generator kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
+    p.LD = P.LD;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    if (p.nt == 2) p.nt = 0;  // (plain or nontemporal block stores; the hand-written write-through store is kernel 3's and 4's)
+    const long long grid = items * P.U;
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    typedef void (*kern_t)(const KParams, const int, const int, const int);
+    const kern_t kern = want_jac ? (kern_t)pcl_pade_large_kernel<true> : (kern_t)pcl_pade_large_kernel<false>;
+    if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 7 : 8, P.lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg, P.npc);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_kernel = (want_jac ? 290 : 280) + p.q;
     ctx->last_n_stream = 0;
     return PCL_OK;
 }
@@ -1510,6 +1618,10 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
+    if (ctx->large) {
+        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context created with PCL_LARGE_N");
+        return launch_pade_large(ctx, p, want_jac);
+    }
     if (ctx->exp) {
         if (want_jac && compact) return launch_exp(ctx, p, true, PCL_EXP_COMPACT);
         // the payload-fused call (pcl_eval_jac_merit_dev, option exp_full): every member, so that the partial sums are numbered as the sum kernel reads them
@@ -2405,12 +2517,14 @@ extern "C" int pcl_jac_dev(pcl_ctx *ctx, const double *Z, double *vals) {  // ev
 extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *delta, double *compact) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !compact) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_compact_dev: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_eval_jac_compact_dev");
     EXP_FULL_GATE(ctx, "pcl_eval_jac_compact_dev");
     return launch_fused(ctx, Z, delta, compact, true);
 }
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_jac_expand_dev");
     VAR_COMPACT_GATE(ctx, "pcl_jac_expand_dev");
     EXP_FULL_GATE(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
@@ -2453,12 +2567,14 @@ extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *v
 extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess_dev: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_hess_dev");
     return launch_hess(ctx, Z, mu, vals);
 }
 
 extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_rollout_dev");
     VAR_GATE(ctx, "pcl_rollout_dev");
     if (ctx->var) return var_rollout_dev(ctx, Z, X_out);
     ON_DEVICE(ctx);
@@ -2534,7 +2650,7 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
     // (variational contexts without the option var_compact, and exponential ones without the option exp_full: full values, host_path 1)
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->large && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -2627,6 +2743,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_hess");
     VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     ON_DEVICE(ctx);
@@ -2646,6 +2763,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
 extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout: NULL pointer");
+    LARGE_NOTIMPL(ctx, "pcl_rollout");
     VAR_GATE(ctx, "pcl_rollout");
     ON_DEVICE(ctx);
     const long long nv = (long long)ctx->win_count * ctx->desc.N * ctx->x_dim;

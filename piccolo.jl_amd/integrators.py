@@ -83,7 +83,8 @@ class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
-                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False):  # fmt: skip
+                 global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
+                 large_generator=False):  # fmt: skip
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order, batch_mode)
@@ -105,8 +106,8 @@ class _PclContext:
         xo = np.ascontiguousarray(np.asarray(x_offs, dtype=np.int32).reshape(-1))
         desc = _lib.pcl_desc(
             struct_size=ctypes.sizeof(_lib.pcl_desc), d=d, n_drives=m, N=N, z_dim=z_dim, u_off=u_off, dt_off=dt_off,
-            batch=batch, batch_mode=batch_mode, pade_order=pade_order, device_id=device, index_base=index_base,
-            per_member_G0=int(bool(per_member_G0)), state_cols=state_cols, global_dim=global_dim,
+            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0), pade_order=pade_order, device_id=device,
+            index_base=index_base, per_member_G0=int(bool(per_member_G0)), state_cols=state_cols, global_dim=global_dim,
             G0=g0.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
             Gj=gj.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
             x_offs=xo.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
@@ -132,11 +133,15 @@ class _PclContext:
         self.var_compact = False  # (the same on a variational context, of either constraint kind)
         self.hess_nnz = self.hess_per = 0
         self.compact_nnz = self.compact_per = 0
+        # ``large_generator`` (the flag PCL_LARGE_N) at a generator dimension above 64: residual and Jacobian only -- the Hessian of the Lagrangian,
+        # the compact Jacobian, the merit / reduce payload, the rollout and the objective raise with the library's message.  At n <= 64 the
+        # flag changes nothing
+        self.large = bool(large_generator) and n > 64
         if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
             self.set_option("var_exp_hess_tiles", 1)
         if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
             self.set_option("var_exp_hess" if batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess", 1)
-        if self.exponential and not self.exp_hessian:
+        if (self.exponential and not self.exp_hessian) or self.large:
             self.hess_nnz = self.hess_per = 0
         else:
             self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
@@ -146,7 +151,7 @@ class _PclContext:
         if var_compact:
             self.set_option("var_compact", 1)
         # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
-        if batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) and not self.exponential:
+        if batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) and not self.exponential and not self.large:
             self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
             self.compact_nnz, self.compact_per = a.value, b.value
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
@@ -297,6 +302,8 @@ class _PclContext:
         if self.exp_hessian:
             self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz = a.value
+        if self.large:  # (neither a Hessian of the Lagrangian nor a compact Jacobian)
+            return
         if self.exponential:  # (the compact Jacobian by ``exp_full`` only, the Hessian of the Lagrangian by ``exp_hessian`` only)
             if self.exp_full:
                 self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
@@ -531,7 +538,7 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False, var_compact=False):
+                 exp_full=False, var_compact=False, large_generator=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -543,7 +550,11 @@ class HipPadeIntegrator:
         (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62.
         ``exp_full=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the compact Jacobian, the host-pointer calls' compact path and the
         merit / reduce payload are served on that constraint too (the library's option ``exp_full``).
-        ``var_compact`` belongs to the variational constructors: ``True`` here is a ``ValueError``."""
+        ``var_compact`` belongs to the variational constructors: ``True`` here is a ``ValueError``.
+        ``large_generator=True`` sets the library's flag ``PCL_LARGE_N``: generator dimensions 66 .. 128 (a transmon with a cavity, density vectors of
+        9 .. 11 levels) on the Pade constraint, residual and Jacobian only -- ``hessian_structure`` / ``eval_hessian_of_lagrangian``, the rollout and the
+        objective raise; solve with a quasi-Newton Hessian.  Never set on its own: without it such a system is refused as before.  With
+        ``pade_order="exp"`` the library refuses it.  At a dimension up to 64 it changes nothing."""
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order)
         _check_var_compact(var_compact)
@@ -586,8 +597,9 @@ class HipPadeIntegrator:
             dt_off=traj.components[traj.timestep].start, x_offs=[traj.components[nm].start for nm in x_names],
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
-            state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full,
+            state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
         )  # fmt: skip
+        self._large_generator = bool(large_generator)
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
         self._state_cols = _lib.PCL_STATE_VECTOR if vec else cols
@@ -616,7 +628,7 @@ class HipPadeIntegrator:
             raise NotImplementedError("f is defined for single-state integrators")
         if self._f_ctx is None:
             self._f_ctx = _PclContext(d=c.d, m=c.m, N=2, z_dim=c.x_dim + 1 + c.m, u_off=c.x_dim + 1, dt_off=c.x_dim,
-                                      x_offs=[0], G0=self.G_drift, Gj=self.G_drives, batch=1,
+                                      x_offs=[0], G0=self.G_drift, Gj=self.G_drives, batch=1, large_generator=self._large_generator,
                                       batch_mode=PCL_BATCH_MEMBERS, state_cols=self._state_cols, pade_order=_resolved_order(c))  # fmt: skip
         z = np.zeros((2, c.x_dim + 1 + c.m))
         z[0, : c.x_dim], z[0, c.x_dim], z[0, c.x_dim + 1 :] = x, dt, np.asarray(u)[: c.m]

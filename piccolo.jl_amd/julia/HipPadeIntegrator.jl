@@ -85,19 +85,22 @@ end
 
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
-                      exp_hessian::Bool = false, exp_full::Bool = false)
+                      exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false)
+    # large_generator = true: the library's flag PCL_LARGE_N in batch_mode -- generator dimensions 66 .. 128 on the Pade constraint, residual and
+    # Jacobian only (no Hessian of the Lagrangian: hess_per = 0, solve with eval_hessian = false).  Never set on its own; at n <= 64 it changes nothing.
     # state_cols: 0 unitary (n = 2d), 1 ket, -1 = PCL_STATE_VECTOR (general n x n generator on one real column, d := n)
     (exp_full && pade_order != PCL_ORDER_EXP) &&
         throw(ArgumentError("HipPadeIntegrator: exp_full = true serves the compact Jacobian and the merit / reduce payload of the exponential constraint: it needs pade_order = :exp"))
     (exp_hessian && pade_order != PCL_ORDER_EXP) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian = true is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order = :exp"))
     n = size(G0s[1], 1); d = state_cols == -1 ? n : n ÷ 2; m = length(Gjs)
+    large = large_generator && n > 64
     G0 = reduce(vcat, [vec(G) for G in G0s])                       # column-major, one block per member
     Gj = m == 0 ? zeros(1) : reduce(vcat, [vec(G) for G in Gjs])
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve G0 Gj x_offs begin
         desc = PclDesc(sizeof(PclDesc), d, m, N, z_dim, u_off, dt_off,
-                       length(x_offs), 0 #= PCL_BATCH_MEMBERS =#, pade_order #= 2, 4, 6, 8 or 10 =#, device, 1 #= 1-based =#,
+                       length(x_offs), (large_generator ? PCL_LARGE_N : 0) #= PCL_BATCH_MEMBERS [| PCL_LARGE_N] =#, pade_order #= 2, 4, 6, 8 or 10 =#, device, 1 #= 1-based =#,
                        length(G0s) > 1 ? 1 : 0, state_cols, global_dim,
                        pointer(G0), pointer(Gj), pointer(x_offs))
         rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
@@ -114,7 +117,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_hess", 1))
     # (exp_full: the library's option of that name -- the host-pointer calls below then move the compact values over PCIe and expand on the host)
     exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
-    (pade_order == PCL_ORDER_EXP && !exp_hessian) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    ((pade_order == PCL_ORDER_EXP && !exp_hessian) || large) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     return core, Int(ncol[])
@@ -182,6 +185,7 @@ end
 # the compact path (one -E per interval over PCIe, replicated by the host's threads) with the bits of the full path, and the compact /
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
+const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128, residual and Jacobian only
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
