@@ -210,12 +210,20 @@ typedef enum pcl_status {
  * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
  * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, and pade_order = 0 with
  * pcl_set_order_policy / pcl_set_order_from_trajectory.  PCL_ENOTIMPL, each message naming PCL_LARGE_N: pcl_hess[_dev], pcl_hess_nnz,
- * pcl_hess_structure[_i64] (solve with a quasi-Newton Hessian, the reference's eval_hessian = false), the compact Jacobian trio, the merit /
+ * pcl_hess_structure[_i64] (unless the option "large_hess" is on: below), the compact Jacobian trio, the merit /
  * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev), pcl_rollout[_dev] and
  * the objective family (goals, weights, regularisers, pcl_infidelity_dev, pcl_objective[_dev], pcl_objective_hess_*).
- * Options: "cols_per_slice" caps the state columns per workgroup, "general_slices" sets the least number of workgroups per interval;
- * "kernel_version", "general_kernel_version", "general_threads", "use_mfma", "nt" = 2 have no effect.  get_option "last_kernel" reads 290 + q
- * after a Jacobian launch and 280 + q after a residual-only launch (q = pade_order / 2). */
+ * The Hessian of the Lagrangian: pcl_set_option "large_hess" = 1 (0 by default, never on by itself; PCL_EINVAL on a context that is not large)
+ * makes pcl_hess[_dev], pcl_hess_nnz and pcl_hess_structure[_i64] serve a large context -- values, order and structure those of every other
+ * Pade context, at orders 2 .. 10, both batch modes, the member window (pcl_kernel_pade_large_hess.hpp: a forward Horner chain and backward
+ * chains on G^T, per-column partial sums added in column order by a second launch; no atomics, every work split bitwise equal; DESIGN.md
+ * 4.18).  Its device workspace (batch x (N - 1) x state columns x (m^2 + m + 1) doubles) is allocated when the option is first set to 1.
+ * Back at 0 the refusals return; without the option solve with a quasi-Newton Hessian (the reference's eval_hessian = false).
+ * Options: "cols_per_slice" caps the state columns per workgroup (both launches), "general_slices" sets the least number of workgroups per
+ * interval of the Jacobian launch, "large_hess_drives" caps the drives per workgroup of the Hessian launch (0 auto; PCL_EINVAL when negative or
+ * off a large context); "kernel_version", "general_kernel_version", "general_threads", "use_mfma", "hess_kernel", "nt" = 2 have no effect.
+ * get_option "last_kernel" reads 290 + q after a Jacobian launch and 280 + q after a residual-only launch, "last_hess_kernel" 290 + q after a
+ * Hessian launch (q = pade_order / 2). */
 #define PCL_LARGE_N 0x100
 #define PCL_LARGE_MAX_N 128
 

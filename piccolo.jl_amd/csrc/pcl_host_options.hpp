@@ -47,6 +47,18 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         else
             ctx->var_exp_hess = 0;
     }
+    else if (!strcmp(key, "large_hess")) {  // large contexts (PCL_LARGE_N, n > 64): serve the Hessian of the Lagrangian (0: refuse it, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "large_hess must be 0 or 1");
+        if (v && !ctx->large) return fail(ctx, PCL_EINVAL, "large_hess = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64); every other context has its Hessian options of its own");
+        if (v)
+            TRY(large_hess_enable(ctx));
+        else
+            ctx->large_hess = 0;
+    }
+    else if (!strcmp(key, "large_hess_drives")) {  // ... the most drives per group of that launch (0 auto: as many as fit; capped by what fits)
+        if (v < 0 || !ctx->large) return fail(ctx, PCL_EINVAL, "large_hess_drives must be >= 0, on a large context (PCL_LARGE_N, generator dimension above 64)");
+        ctx->opt_large_hess_drives = v;
+    }
     else if (!strcmp(key, "var_exp_hess_tiles")) {  // ... where the octuple chain's tiles live: 0 nine in LDS | 1 four in the workspace where nine do not fit | 2 always
         TRY(var_exp_hess_set_tiles(ctx, v));
     }
@@ -195,6 +207,10 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->var_exp_hess;
     else if (!strcmp(key, "var_exp_hess_tiles"))
         *v = ctx->opt_vexph_tiles;
+    else if (!strcmp(key, "large_hess"))
+        *v = ctx->large_hess;
+    else if (!strcmp(key, "large_hess_drives"))
+        *v = ctx->opt_large_hess_drives;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

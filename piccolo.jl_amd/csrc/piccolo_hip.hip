@@ -6,6 +6,7 @@
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
+//   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
 //   pcl_kernels_hessian.hpp    Hessian of the Lagrangian: versions 1 (one workgroup per interval) and 2 (column chunks, fallback)
 //   pcl_kernel_hessian_v3.hpp  Hessian of the Lagrangian, default: one workgroup per interval, jobs split by drive
 //   pcl_kernels_misc.hpp       compact -> full expansion, rollout, derivative / time rows, terminal infidelity
@@ -45,6 +46,7 @@
 #include "pcl_kernels_reference.hpp"
 #include "pcl_kernel_pade_v2.hpp"
 #include "pcl_kernel_pade_large.hpp"
+#include "pcl_kernel_pade_large_hess.hpp"
 #include "pcl_kernels_fused_v2.hpp"
 #include "pcl_kernel_fused_v3.hpp"
 #include "pcl_kernel_eval.hpp"
@@ -68,7 +70,10 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
-    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); Hessian, compact Jacobian, merit / reduce, rollout and objective are refused
+    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every residual / Jacobian launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); compact Jacobian, merit / reduce, rollout and objective are refused, and so is the Hessian of the Lagrangian without the option below
+    int large_hess = 0;                    // ... option large_hess: the Hessian of the Lagrangian is served (pcl_kernel_pade_large_hess.hpp)
+    int64_t opt_large_hess_drives = 0;     // ... ... the most drives per group of that launch (0 auto: as many as fit)
+    double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
     int exp_full = 0;            // ... option exp_full: the compact Jacobian trio, the host expansion and the merit / reduce payload are served
@@ -271,8 +276,8 @@ struct pcl_ctx {
     int64_t last_n_stream = 0;  // stream-role workgroups of the last kernel-3 launch (0: fused roles / round-robin)
     int64_t last_kernel = 0;  // 10*version + (1 if shape-specialised) of the last fused launch
     int64_t opt_grid = 0;  // 0: resident workgroups (persistent kernel)
-    size_t lds_set[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const void *lds_kern[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // last MaxDynamicSharedMemorySize set per kernel variant
+    size_t lds_set[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const void *lds_kern[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // last MaxDynamicSharedMemorySize set per kernel variant
     int max_lds = 0;
     int n_cu = 0;
     // order policy (pade_order = 0 in the descriptor): host copies of the generators for the norm bound, the tolerance, what was found
@@ -383,6 +388,12 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
     do {                                                                                                                                                  \
         if ((ctx) && (ctx)->large)                                                                                                                        \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
+    } while (0)
+
+// ... its Hessian of the Lagrangian by option large_hess only (pcl_kernel_pade_large_hess.hpp): without it, the same words
+#define LARGE_HESS_GATE(ctx, what)                                \
+    do {                                                          \
+        if ((ctx) && !(ctx)->large_hess) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
 #define EXP_HESS_GATE(ctx, what)                       \
@@ -714,7 +725,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);
@@ -786,7 +797,7 @@ extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *pe
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    LARGE_NOTIMPL(ctx, "pcl_hess_nnz");
+    LARGE_HESS_GATE(ctx, "pcl_hess_nnz");
     VAR_EXP_NOHESS(ctx, "pcl_hess_nnz");
     EXP_HESS_GATE(ctx, "pcl_hess_nnz");
     if (per) *per = hess_per(ctx);
@@ -857,7 +868,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
-    LARGE_NOTIMPL(ctx, "pcl_hess_structure");
+    LARGE_HESS_GATE(ctx, "pcl_hess_structure");
     VAR_EXP_NOHESS(ctx, "pcl_hess_structure");
     EXP_HESS_GATE(ctx, "pcl_hess_structure");
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
@@ -1243,6 +1254,82 @@ static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac) {
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_kernel = (want_jac ? 290 : 280) + p.q;
     ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
+// Hessian of the Lagrangian of a large context (pcl_kernel_pade_large_hess.hpp; option large_hess).  The plan: beside the tile (LD = n | 1) a
+// unit of nc state columns and mg drives holds nc (10 + 4 mg) column blocks of LD doubles (-S, D, Z_1 .. Z_4, W twice, V twice per drive, the
+// four families of accumulators) and nc (mg (m + 1) + 1) partial sums.  The widest nc that leaves room for one drive is taken (option
+// cols_per_slice caps it), then the most drives per group that fit (option large_hess_drives caps them); slices and groups are evened.  One
+// column and one drive always fit (n = 128, m = 24: 148,032 B).  Every split gives the same bits.
+struct LargeHessPlan {
+    int LD, threads, sx, nc, mg, ngrp, U;
+    size_t lds;
+};
+static size_t large_hess_lds_bytes(int n, int m, int nc, int mg) {
+    const size_t LD = (size_t)(n | 1);
+    return (LD * n + LD * nc * (10 + 4 * (size_t)mg) + PL_SLACK + m + 8 + (size_t)nc * ((size_t)mg * (m + 1) + 1)) * sizeof(double);
+}
+static void large_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeHessPlan &P) {
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
+    const int mg_cap = m > 0 ? (ctx->opt_large_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_hess_drives, m) : m) : 0;
+    const int mg_min = m > 0 ? 1 : 0;
+    P.nc = 1;
+    for (int nc = nc_cap; nc > 1; --nc)
+        if (large_hess_lds_bytes(n, m, nc, mg_min) <= (size_t)ctx->max_lds) {
+            P.nc = nc;
+            break;
+        }
+    P.mg = mg_min;
+    for (int mg = mg_cap; mg > mg_min; --mg)
+        if (large_hess_lds_bytes(n, m, P.nc, mg) <= (size_t)ctx->max_lds) {
+            P.mg = mg;
+            break;
+        }
+    P.ngrp = m > 0 ? (m + P.mg - 1) / P.mg : 1;
+    if (m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
+    P.sx = (cols + P.nc - 1) / P.nc;
+    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.U = P.sx * P.ngrp;
+    P.lds = large_hess_lds_bytes(n, m, P.nc, P.mg);
+}
+static int large_hess_enable(pcl_ctx *ctx) {
+    if (!ctx->dlhpart) {
+        ON_DEVICE(ctx);
+        const long long m = ctx->desc.n_drives;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dlhpart, (size_t)ctx->desc.batch * ctx->K * ctx->cols * (m * (m + 1) + 1) * sizeof(double)));
+    }
+    ctx->large_hess = 1;
+    return PCL_OK;
+}
+static int resolve_order(pcl_ctx *ctx, const double *Z_host, const char *where);
+static int launch_pade_large_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    if (int rc = resolve_order(ctx, nullptr, "pcl_hess")) return rc;
+    KParams p;
+    fill_params(ctx, p);
+    fill_pade(p, ctx->desc.pade_order);
+    p.Z = Z + (ctx->desc.batch_mode == PCL_BATCH_TRAJ ? (long long)ctx->win_first * ctx->desc.z_dim * ctx->desc.N : 0);
+    p.mu = mu;
+    p.hess = hess;
+    p.hpart = ctx->dlhpart;
+    LargeHessPlan P;
+    large_hess_plan(ctx, p.n, p.cols, p.m, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large-generator Hessian kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
+    p.LD = P.LD;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    const long long items = (long long)p.batch * p.K, grid = items * P.U;
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    if (int rc = set_lds_attr(ctx, (const void *)pcl_pade_large_hess_kernel, 9, P.lds)) return rc;
+    hipLaunchKernelGGL(pcl_pade_large_hess_kernel, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(pcl_pade_large_hess_sum_kernel, dim3((unsigned)items), dim3(256), 0, ctx->stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_hess_kernel = 290 + p.q;
     return PCL_OK;
 }
 
@@ -1901,6 +1988,8 @@ static size_t hess2_lds_bytes(const KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
+    LARGE_HESS_GATE(ctx, "pcl_hess");
+    if (ctx->large) return launch_pade_large_hess(ctx, Z, mu, hess);
     VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);
@@ -2567,7 +2656,7 @@ extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *v
 extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess_dev: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_hess_dev");
+    LARGE_HESS_GATE(ctx, "pcl_hess_dev");
     return launch_hess(ctx, Z, mu, vals);
 }
 
@@ -2743,7 +2832,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_hess");
+    LARGE_HESS_GATE(ctx, "pcl_hess");
     VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");
     ON_DEVICE(ctx);

@@ -85,7 +85,14 @@ end
 
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
-                      exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false)
+                      exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
+                      large_hessian::Bool = false)
+    # large_hessian = true (with large_generator = true on the Pade constraint only): the library's option large_hess -- the Hessian of the
+    # Lagrangian at those dimensions too (hess_per > 0, eval_hessian = true works).  At n <= 64 the ordinary context serves its Hessian as always.
+    (large_hessian && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_hessian = true is the Hessian of the Lagrangian of a context created with large_generator = true: it needs that keyword"))
+    (large_hessian && pade_order == PCL_ORDER_EXP) &&
+        throw(ArgumentError("HipPadeIntegrator: large_hessian = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large contexts"))
     # large_generator = true: the library's flag PCL_LARGE_N in batch_mode -- generator dimensions 66 .. 128 on the Pade constraint, residual and
     # Jacobian only (no Hessian of the Lagrangian: hess_per = 0, solve with eval_hessian = false).  Never set on its own; at n <= 64 it changes nothing.
     # state_cols: 0 unitary (n = 2d), 1 ket, -1 = PCL_STATE_VECTOR (general n x n generator on one real column, d := n)
@@ -117,7 +124,8 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_hess", 1))
     # (exp_full: the library's option of that name -- the host-pointer calls below then move the compact values over PCIe and expand on the host)
     exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
-    ((pade_order == PCL_ORDER_EXP && !exp_hessian) || large) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    (large && large_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_hess", 1))
+    ((pade_order == PCL_ORDER_EXP && !exp_hessian) || (large && !large_hessian)) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     return core, Int(ncol[])
@@ -185,7 +193,7 @@ end
 # the compact path (one -E per interval over PCIe, replicated by the host's threads) with the bits of the full path, and the compact /
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
-const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128, residual and Jacobian only
+const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -285,7 +293,8 @@ end
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false)
+                      var_compact::Bool = false, large_hessian::Bool = false)
+    large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
     (exp_hessian isa Symbol && exp_hessian != :workspace) &&
