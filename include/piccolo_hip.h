@@ -211,19 +211,29 @@ typedef enum pcl_status {
  * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, and pade_order = 0 with
  * pcl_set_order_policy / pcl_set_order_from_trajectory.  PCL_ENOTIMPL, each message naming PCL_LARGE_N: pcl_hess[_dev], pcl_hess_nnz,
  * pcl_hess_structure[_i64] (unless the option "large_hess" is on: below), the compact Jacobian trio, the merit /
- * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev), pcl_rollout[_dev] and
- * the objective family (goals, weights, regularisers, pcl_infidelity_dev, pcl_objective[_dev], pcl_objective_hess_*).
+ * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev), and -- unless the
+ * option "large_full" is on: below -- pcl_rollout[_dev] and the objective family (goals, weights, regularisers, pcl_infidelity_dev,
+ * pcl_objective[_dev], pcl_objective_hess_*).
  * The Hessian of the Lagrangian: pcl_set_option "large_hess" = 1 (0 by default, never on by itself; PCL_EINVAL on a context that is not large)
  * makes pcl_hess[_dev], pcl_hess_nnz and pcl_hess_structure[_i64] serve a large context -- values, order and structure those of every other
  * Pade context, at orders 2 .. 10, both batch modes, the member window (pcl_kernel_pade_large_hess.hpp: a forward Horner chain and backward
  * chains on G^T, per-column partial sums added in column order by a second launch; no atomics, every work split bitwise equal; DESIGN.md
  * 4.18).  Its device workspace (batch x (N - 1) x state columns x (m^2 + m + 1) doubles) is allocated when the option is first set to 1.
  * Back at 0 the refusals return; without the option solve with a quasi-Newton Hessian (the reference's eval_hessian = false).
- * Options: "cols_per_slice" caps the state columns per workgroup (both launches), "general_slices" sets the least number of workgroups per
- * interval of the Jacobian launch, "large_hess_drives" caps the drives per workgroup of the Hessian launch (0 auto; PCL_EINVAL when negative or
+ * The objective and the rollout: pcl_set_option "large_full" = 1 (0 by default, never on by itself; PCL_EINVAL on a context that is not large,
+ * and for any value outside 0 and 1; independent of "large_hess") makes pcl_set_goal, pcl_set_goal_subspace, pcl_set_goal_form, pcl_set_weights,
+ * pcl_add_regularizer, pcl_clear_regularizers, pcl_infidelity_dev, pcl_objective[_dev], pcl_objective_hess_nnz, pcl_objective_hess_structure,
+ * pcl_objective_hess[_dev] and pcl_rollout[_dev] serve a large context with the contracts of n <= 64 (matrix and subspace goals: unitary states
+ * only; a subspace goal of more than 45 levels is PCL_ESHAPE with the rows or LDS bytes it needs; a unitary goal's Hessian is x_dim (x_dim + 1) / 2
+ * doubles per goal and per evaluation, 268 MB at d = 64, and a failed allocation is PCL_ENOMEM).  The rollout is two launches on the one-tile
+ * plan (pcl_kernel_large_rollout.hpp: propagators by column panels as a substepped degree-18 Taylor polynomial, then the chain of the knots; no
+ * atomics, every work split bitwise equal); its workspace (batch x (N - 1) x n^2 doubles) is allocated at the first rollout.
+ * Back at 0 the refusals return and goal, weights and regularisers are dropped.
+ * Options: "cols_per_slice" caps the state columns per workgroup (Jacobian, Hessian and the rollout's chain), "general_slices" sets the least
+ * number of workgroups per interval of the Jacobian launch and of the rollout's propagator launch, "large_hess_drives" caps the drives per workgroup of the Hessian launch (0 auto; PCL_EINVAL when negative or
  * off a large context); "kernel_version", "general_kernel_version", "general_threads", "use_mfma", "hess_kernel", "nt" = 2 have no effect.
- * get_option "last_kernel" reads 290 + q after a Jacobian launch and 280 + q after a residual-only launch, "last_hess_kernel" 290 + q after a
- * Hessian launch (q = pade_order / 2). */
+ * get_option "last_kernel" reads 290 + q after a Jacobian launch, 280 + q after a residual-only launch and 270 after a rollout,
+ * "last_hess_kernel" 290 + q after a Hessian launch (q = pade_order / 2). */
 #define PCL_LARGE_N 0x100
 #define PCL_LARGE_MAX_N 128
 

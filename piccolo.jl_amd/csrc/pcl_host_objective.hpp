@@ -76,6 +76,7 @@ extern "C" int pcl_deriv_eval_jac(pcl_ctx *ctx, int32_t x_off, int32_t dx_off, i
 }
 
 // --- terminal infidelity objective ----------------------------------------------
+#define PCL_FORM_MAX_ROWS 4096  // rows of the terminal form
 static int objective_unitary_only(const pcl_ctx *ctx, const char *who) {
     if (ctx->vec || ctx->cols != ctx->desc.d) return fail(ctx, PCL_ENOTIMPL, "%s: unitary (n x d) states only", who);
     return PCL_OK;
@@ -141,13 +142,13 @@ static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int
     return set_form(ctx, 0, R, A.data(), nullptr, false);
 }
 extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c) {
-    LARGE_NOTIMPL(ctx, "pcl_set_goal_form");
+    LARGE_FULL_GATE(ctx, "pcl_set_goal_form");
     VAR_GATE(ctx, "pcl_set_goal_form");
     if (ctx && ctx->var) return var_set_goal_form(ctx, scope, R, A, c);
     if (!ctx) return PCL_EINVAL;
     if (scope != 0 && scope != 1) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: scope must be 0 (per member) or 1 (joint)");
     if (scope == 1 && ctx->desc.batch_mode != PCL_BATCH_MEMBERS) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: a joint term needs the members of ONE trajectory buffer");
-    if (R > 4096) return fail(ctx, PCL_ESHAPE, "pcl_set_goal_form: at most 4096 rows");
+    if (R > PCL_FORM_MAX_ROWS) return fail(ctx, PCL_ESHAPE, "pcl_set_goal_form: at most 4096 rows");
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);  // (replaces a unitary goal)
@@ -156,7 +157,7 @@ extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const d
     return set_form(ctx, scope, R, A, c, true);
 }
 extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
-    LARGE_NOTIMPL(ctx, "pcl_set_goal");
+    LARGE_FULL_GATE(ctx, "pcl_set_goal");
     VAR_GATE(ctx, "pcl_set_goal");
     if (ctx && ctx->var) return var_set_goal(ctx, goal_iso_vec);
     if (!ctx) return PCL_EINVAL;
@@ -173,7 +174,7 @@ extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
     return unitary_form(ctx, goal_iso_vec);
 }
 extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns) {
-    LARGE_NOTIMPL(ctx, "pcl_set_goal_subspace");
+    LARGE_FULL_GATE(ctx, "pcl_set_goal_subspace");
     VAR_GATE(ctx, "pcl_set_goal_subspace");
     if (ctx && ctx->var) return var_set_goal_subspace(ctx, goal_sub_iso_vec, subspace, ns);
     if (!ctx) return PCL_EINVAL;
@@ -184,6 +185,13 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
         if (subspace[i] < 0 || subspace[i] >= ctx->desc.d) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: index %d outside 0..d-1", subspace[i]);
         for (int j = 0; j < i; ++j)
             if (subspace[j] == subspace[i]) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: index %d repeated", subspace[i]);
+    }
+    if (ctx->large) {  // (d up to 64: the two sizes no subspace of d <= 32 reaches; refused here, before anything is replaced or launched)
+        const size_t lds = 6 * (size_t)ns * ns * sizeof(double);
+        if (lds > (size_t)ctx->max_lds)
+            return fail(ctx, PCL_ESHAPE, "pcl_set_goal_subspace: a subspace of %d levels needs %zu B of LDS in the infidelity kernel (six %d x %d blocks), %d B are available: 58 levels at most", ns, lds, ns, ns, ctx->max_lds);
+        if (2 * ns * ns + 2 > PCL_FORM_MAX_ROWS)
+            return fail(ctx, PCL_ESHAPE, "pcl_set_goal_subspace: a subspace of %d levels needs %d rows of the terminal form (2 ns^2 + 2), %d are available: 45 levels at most", ns, 2 * ns * ns + 2, PCL_FORM_MAX_ROWS);
     }
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -201,7 +209,7 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
 }
 extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
-    LARGE_NOTIMPL(ctx, "pcl_set_weights");
+    LARGE_FULL_GATE(ctx, "pcl_set_weights");
     VAR_GATE(ctx, "pcl_set_weights");
     if (ctx && ctx->var) return var_set_weights(ctx, w);
     if (!ctx) return PCL_EINVAL;
@@ -218,7 +226,7 @@ extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
     return PCL_OK;
 }
 extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const double *R, int32_t dt_power) {
-    LARGE_NOTIMPL(ctx, "pcl_add_regularizer");
+    LARGE_FULL_GATE(ctx, "pcl_add_regularizer");
     VAR_GATE(ctx, "pcl_add_regularizer");
     if (!ctx) return PCL_EINVAL;
     if (!R || dim < 1 || off < 0 || off + dim > ctx->desc.z_dim) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: component [%d, %d) outside the knot (z_dim=%d)", off, off + dim, ctx->desc.z_dim);
@@ -231,7 +239,7 @@ extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const
     return PCL_OK;
 }
 extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
-    LARGE_NOTIMPL(ctx, "pcl_clear_regularizers");
+    LARGE_FULL_GATE(ctx, "pcl_clear_regularizers");
     VAR_GATE(ctx, "pcl_clear_regularizers");
     if (!ctx) return PCL_EINVAL;
     ctx->regs.clear();
@@ -240,8 +248,13 @@ extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
     return PCL_OK;
 }
 static unsigned infidelity_lds(const pcl_ctx *ctx) { return (unsigned)(6 * (size_t)ctx->n_sub * ctx->n_sub * sizeof(double)); }
+// a subspace of 37 levels or more (large contexts only: d > 32) takes more dynamic LDS than a kernel may have without asking
+static int infidelity_lds_attr(pcl_ctx *ctx, const void *kern, size_t lds) {
+    if (lds > 65536) HIP_TRY(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return PCL_OK;
+}
 extern "C" int pcl_infidelity_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_NOTIMPL(ctx, "pcl_infidelity_dev");
+    LARGE_FULL_GATE(ctx, "pcl_infidelity_dev");
     VAR_NOTIMPL(ctx, "pcl_infidelity_dev");
     if (!ctx) return PCL_EINVAL;
     if (!Z || (!value && !grad)) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: NULL pointer");
@@ -249,6 +262,7 @@ extern "C" int pcl_infidelity_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
     TRY(objective_unitary_only(ctx, "pcl_infidelity_dev"));
     ON_DEVICE(ctx);
     const pcl_desc &D = ctx->desc;
+    TRY(infidelity_lds_attr(ctx, (const void *)pcl_infidelity_kernel, infidelity_lds(ctx)));
     hipLaunchKernelGGL(pcl_infidelity_kernel, dim3((unsigned)D.batch), dim3(256), infidelity_lds(ctx), ctx->stream, Z, ctx->dgoal, ctx->dsub,
                        ctx->n_sub, ctx->dxoffs, ctx->dweights, value, grad, (long long)ctx->x_dim, 0, Q, D.d, D.N, D.z_dim,
                        D.batch_mode == PCL_BATCH_TRAJ ? (long long)D.z_dim * D.N : 0LL, PclObjSum{nullptr, nullptr, nullptr, 0, 0, 0, 0});
@@ -289,7 +303,7 @@ static int objective_prepare(pcl_ctx *ctx) {
 static bool tail_applies(const pcl_ctx *ctx, const double *grad, int &lo_, int &hi_);
 static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad, int skip_lo, int skip_hi, double *merit_out);
 extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_NOTIMPL(ctx, "pcl_objective_dev");
+    LARGE_FULL_GATE(ctx, "pcl_objective_dev");
     VAR_GATE(ctx, "pcl_objective_dev");
     if (ctx && ctx->var) return var_objective_dev(ctx, Z, Q, value, grad);
     if (!ctx) return PCL_EINVAL;
@@ -334,6 +348,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
                        (int)ctx->regs.size(), (const double *)ctx->dreg_R, grad, regval, D.N, D.z_dim, D.dt_off, zs);
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->dgoal) {
+        TRY(infidelity_lds_attr(ctx, (const void *)pcl_infidelity_kernel, infidelity_lds(ctx)));
         hipLaunchKernelGGL(pcl_infidelity_kernel, dim3((unsigned)D.batch), dim3(256), infidelity_lds(ctx), ctx->stream, Z, ctx->dgoal,
                            ctx->dsub, ctx->n_sub, ctx->dxoffs, ctx->dweights, member, grad, traj ? (long long)D.z_dim * D.N : 0LL, 1, Q, D.d,
                            D.N, D.z_dim, zs,
@@ -348,7 +363,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
     return PCL_OK;
 }
 extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_NOTIMPL(ctx, "pcl_objective");
+    LARGE_FULL_GATE(ctx, "pcl_objective");
     VAR_GATE(ctx, "pcl_objective");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective: NULL pointer");
@@ -495,8 +510,41 @@ static long long obj_hess_per_knot(const pcl_ctx *ctx) {
     for (const PclReg &r : ctx->regs) n += (long long)r.dim * (r.pw >= 1 ? 2 : 1) + (r.pw == 2 ? 1 : 0);
     return n;
 }
+// the Hessian's large arrays (a unitary goal at d = 64: 268 MB for the Gram triangle, as much per staged evaluation): a failed allocation is
+// PCL_ENOMEM, the pointer stays NULL, the sticky HIP error is cleared and the context goes on as before
+static int obj_hess_alloc(pcl_ctx *ctx, double **buf, long long count, const char *what) {
+    const hipError_t e = hipMalloc((void **)buf, (size_t)count * sizeof(double));
+    if (e == hipSuccess) return PCL_OK;
+    *buf = nullptr;
+    (void)hipGetLastError();
+    return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "%s (%lld doubles): %s", what, count, hipGetErrorString(e));
+}
+// option large_full (large contexts): 1 serves the objective family and the rollout; 0 refuses them again and drops goal, weights and regularisers
+static int large_set_full(pcl_ctx *ctx, int64_t on) {
+    if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "large_full must be 0 or 1");
+    if (!ctx->large)
+        return on ? fail(ctx, PCL_EINVAL, "large_full = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64, on the Pade constraint); every other context serves its objective and rollout without it or by an option of its own")
+                  : PCL_OK;
+    if ((int)on == ctx->large_full) return PCL_OK;
+    ON_DEVICE(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (double **q : {&ctx->dgoal, &ctx->dweights, &ctx->dformA, &ctx->dformc, &ctx->dgram, &ctx->dcoef}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    if (ctx->dsub) (void)hipFree(ctx->dsub);
+    ctx->dsub = nullptr;
+    ctx->n_sub = 0;
+    ctx->form_R = ctx->form_L = ctx->form_scope = 0;
+    ctx->form_user = ctx->gram_ready = false;
+    ctx->regs.clear();
+    ctx->reg_R.clear();
+    ctx->regs_dirty = true;
+    ctx->large_full = (int)on;
+    return PCL_OK;
+}
 extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
-    LARGE_NOTIMPL(ctx, "pcl_objective_hess_nnz");
+    LARGE_FULL_GATE(ctx, "pcl_objective_hess_nnz");
     VAR_GATE(ctx, "pcl_objective_hess_nnz");
     if (ctx && ctx->var) return var_objective_hess_nnz(ctx, nnz);
     if (!ctx || !nnz) return PCL_EINVAL;
@@ -505,7 +553,7 @@ extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols) {
-    LARGE_NOTIMPL(ctx, "pcl_objective_hess_structure");
+    LARGE_FULL_GATE(ctx, "pcl_objective_hess_structure");
     VAR_GATE(ctx, "pcl_objective_hess_structure");
     if (ctx && ctx->var) return var_objective_hess_structure(ctx, rows, cols);
     if (!ctx || !rows || !cols) return PCL_EINVAL;
@@ -540,7 +588,7 @@ extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, i
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    LARGE_NOTIMPL(ctx, "pcl_objective_hess_dev");
+    LARGE_FULL_GATE(ctx, "pcl_objective_hess_dev");
     VAR_GATE(ctx, "pcl_objective_hess_dev");
     if (ctx && ctx->var) return var_objective_hess_dev(ctx, Z, Q, sigma, vals);
     if (!ctx) return PCL_EINVAL;
@@ -554,7 +602,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     if (nT) {
         const PclForm f{ctx->dformA, ctx->dformc, ctx->form_R, ctx->form_L, ctx->form_scope};
         if (!ctx->gram_ready) {  // T = 2 sum_r A_r A_r', once per goal
-            if (!ctx->dgram) HIP_TRY(ctx, hipMalloc((void **)&ctx->dgram, (size_t)nT * sizeof(double)));
+            if (!ctx->dgram) TRY(obj_hess_alloc(ctx, &ctx->dgram, nT, "pcl_objective_hess_dev: the Gram triangle"));
             hipLaunchKernelGGL(pcl_gram_kernel, dim3((unsigned)std::min<long long>((nT + 255) / 256, 4096)), dim3(256), 0, ctx->stream, f, ctx->dgram);
             HIP_TRY(ctx, hipGetLastError());
             ctx->gram_ready = true;
@@ -576,7 +624,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    LARGE_NOTIMPL(ctx, "pcl_objective_hess");
+    LARGE_FULL_GATE(ctx, "pcl_objective_hess");
     VAR_GATE(ctx, "pcl_objective_hess");
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess: NULL pointer");
@@ -586,7 +634,7 @@ extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, doubl
     if (nnz == 0) return PCL_OK;
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     double *dv = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&dv, (size_t)nnz * sizeof(double)));
+    TRY(obj_hess_alloc(ctx, &dv, nnz, "pcl_objective_hess: the staged values"));
     int rc = PCL_OK;
     if (hipMemcpyAsync(ctx->dZ, Z, z_len(ctx) * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = PCL_EHIP;
     if (rc == PCL_OK) rc = pcl_objective_hess_dev(ctx, ctx->dZ, Q, sigma, dv);
@@ -662,6 +710,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
     a.skip_lo = skip_lo;
     a.skip_hi = skip_hi;
     const size_t lds = std::max((size_t)infidelity_lds(ctx), merit_out ? (size_t)D.batch * (m + 2) * sizeof(double) : (size_t)0);
+    TRY(infidelity_lds_attr(ctx, (const void *)pcl_ens_tail_kernel, lds));
     hipLaunchKernelGGL(pcl_ens_tail_kernel, dim3((unsigned)(nbuf * D.N + D.batch + a.K)), dim3(256), lds, ctx->stream, a);
     HIP_TRY(ctx, hipGetLastError());
     return PCL_OK;

@@ -59,6 +59,13 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v < 0 || !ctx->large) return fail(ctx, PCL_EINVAL, "large_hess_drives must be >= 0, on a large context (PCL_LARGE_N, generator dimension above 64)");
         ctx->opt_large_hess_drives = v;
     }
+    else if (!strcmp(key, "large_full")) {  // large contexts: serve the objective family and the rollout (0: refuse them, the default, and drop goal, weights, regularisers)
+        TRY(large_set_full(ctx, v));
+    }
+    else if (!strcmp(key, "large_rollout_stage")) {  // ... measurements (bench/bench_large_full.py): 0 both launches of the rollout | 1 the propagators only | 2 the chain only
+        if (v < 0 || v > 2 || !ctx->large) return fail(ctx, PCL_EINVAL, "large_rollout_stage must be 0, 1 or 2, on a large context (PCL_LARGE_N, generator dimension above 64)");
+        ctx->opt_large_rollout_stage = v;
+    }
     else if (!strcmp(key, "var_exp_hess_tiles")) {  // ... where the octuple chain's tiles live: 0 nine in LDS | 1 four in the workspace where nine do not fit | 2 always
         TRY(var_exp_hess_set_tiles(ctx, v));
     }
@@ -211,6 +218,10 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->large_hess;
     else if (!strcmp(key, "large_hess_drives"))
         *v = ctx->opt_large_hess_drives;
+    else if (!strcmp(key, "large_full"))
+        *v = ctx->large_full;
+    else if (!strcmp(key, "large_rollout_stage"))
+        *v = ctx->opt_large_rollout_stage;
     else if (!strcmp(key, "host_threads"))
         *v = host_threads(ctx);
     else if (!strcmp(key, "host_expand_MBps"))  // delivered rate of the fastest call of the thread-count sweep (0 before it has finished)

@@ -6,6 +6,7 @@
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
+//   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
 //   pcl_kernels_hessian.hpp    Hessian of the Lagrangian: versions 1 (one workgroup per interval) and 2 (column chunks, fallback)
 //   pcl_kernel_hessian_v3.hpp  Hessian of the Lagrangian, default: one workgroup per interval, jobs split by drive
@@ -47,6 +48,7 @@
 #include "pcl_kernel_pade_v2.hpp"
 #include "pcl_kernel_pade_large.hpp"
 #include "pcl_kernel_pade_large_hess.hpp"
+#include "pcl_kernel_large_rollout.hpp"
 #include "pcl_kernels_fused_v2.hpp"
 #include "pcl_kernel_fused_v3.hpp"
 #include "pcl_kernel_eval.hpp"
@@ -70,9 +72,11 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
-    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every residual / Jacobian launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); compact Jacobian, merit / reduce, rollout and objective are refused, and so is the Hessian of the Lagrangian without the option below
+    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every residual / Jacobian launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); compact Jacobian and merit / reduce are refused, and so are the Hessian of the Lagrangian, the rollout and the objective without the options below
     int large_hess = 0;                    // ... option large_hess: the Hessian of the Lagrangian is served (pcl_kernel_pade_large_hess.hpp)
     int64_t opt_large_hess_drives = 0;     // ... ... the most drives per group of that launch (0 auto: as many as fit)
+    int large_full = 0;                    // ... option large_full: the objective family and the rollout are served (pcl_kernel_large_rollout.hpp; its workspace is dexpm)
+    int64_t opt_large_rollout_stage = 0;   // ... ... measurements: 0 both launches of the rollout | 1 the propagators only | 2 the chain only, on the workspace as it stands
     double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
@@ -383,7 +387,8 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
         if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
     } while (0)
 
-// A large context (PCL_LARGE_N, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is refused in these words.
+// A large context (PCL_LARGE_N, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is refused in these words
+// (the Hessian of the Lagrangian, the objective family and the rollout unless their options are on: the gates below).
 #define LARGE_NOTIMPL(ctx, what)                                                                                                                          \
     do {                                                                                                                                                  \
         if ((ctx) && (ctx)->large)                                                                                                                        \
@@ -394,6 +399,12 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 #define LARGE_HESS_GATE(ctx, what)                                \
     do {                                                          \
         if ((ctx) && !(ctx)->large_hess) LARGE_NOTIMPL(ctx, what); \
+    } while (0)
+
+// ... and the objective family and the rollout by option large_full only (pcl_kernel_large_rollout.hpp): without it, the same words
+#define LARGE_FULL_GATE(ctx, what)                                \
+    do {                                                          \
+        if ((ctx) && !(ctx)->large_full) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
 #define EXP_HESS_GATE(ctx, what)                       \
@@ -2660,12 +2671,84 @@ extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, dou
     return launch_hess(ctx, Z, mu, vals);
 }
 
+// Rollout of a large context (pcl_kernel_large_rollout.hpp; option large_full).  Beside the tile (LD = n | 1) the propagator launch holds three
+// blocks of npc columns of E (Y, V, the product); the chain launch holds two blocks of nc state columns and no tile (its operand E_k goes from the
+// workspace into registers).  The widest panel that fits is evened over the panels; launches of few intervals take up to one panel per 16
+// columns while the grid stays within one round of the CUs (option general_slices: that many panels at least).  The chain takes slices of at most 16 state columns, one matrix-core column tile (option
+// cols_per_slice: that many at most), evened.  One column always fits (n = 128, m = 24: 136,472 B and 3,088 B).  Every split gives the same bits.
+struct LargeRollPlan {
+    int LD, threads, P, npc, S, nc;
+    size_t lds_e, lds_c;
+};
+static void large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, long long items, LargeRollPlan &R) {
+    R.LD = n | 1;
+    R.threads = 64 * ((n + 15) / 16);
+    const long long budget = ctx->max_lds / (long long)sizeof(double), tile = (long long)R.LD * n;
+    const long long fixed_e = tile + PL_SLACK + m + 8, fixed_c = PL_SLACK;
+    const int npc_max = (int)std::max<long long>(1, std::min<long long>(n, (budget - fixed_e) / R.LD / 3));
+    const int p_min = (n + npc_max - 1) / npc_max;
+    const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices : std::min<long long>((n + 15) / 16, ctx->n_cu / std::max(items, 1LL));
+    R.P = (int)std::max<long long>(p_min, std::min<long long>(want, n));
+    R.npc = (n + R.P - 1) / R.P;
+    R.P = (n + R.npc - 1) / R.npc;  // (no panel without a column)
+    const int nc_fit = (int)std::max<long long>(1, (budget - fixed_c) / R.LD / 2);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16);
+    R.nc = std::min(nc_cap, nc_fit);
+    R.S = (cols + R.nc - 1) / R.nc;
+    R.nc = (cols + R.S - 1) / R.S;  // even slices
+    R.lds_e = (size_t)(fixed_e + 3LL * R.LD * R.npc) * sizeof(double);
+    R.lds_c = (size_t)(fixed_c + 2LL * R.LD * R.nc) * sizeof(double);
+}
+static int launch_large_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
+    ON_DEVICE(ctx);
+    KParams p;
+    fill_params(ctx, p);
+    p.Z = Z + (ctx->desc.batch_mode == PCL_BATCH_TRAJ ? (long long)ctx->win_first * ctx->desc.z_dim * ctx->desc.N : 0);
+    p.xout = X_out;
+    if (!ctx->dexpm) {  // the propagators of every member: batch x (N - 1) x n^2 doubles, kept until pcl_destroy
+        const hipError_t e = hipMalloc((void **)&ctx->dexpm, (size_t)ctx->desc.batch * p.K * p.n * p.n * sizeof(double));
+        if (e != hipSuccess) {
+            ctx->dexpm = nullptr;
+            (void)hipGetLastError();
+            return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "pcl_rollout_dev: the propagator workspace of %zu B: %s",
+                        (size_t)ctx->desc.batch * p.K * p.n * p.n * sizeof(double), hipGetErrorString(e));
+        }
+    }
+    p.expm = ctx->dexpm;
+    LargeRollPlan R;
+    const long long items = (long long)p.batch * p.K;
+    large_roll_plan(ctx, p.n, p.cols, p.m, items, R);
+    if (R.lds_e > (size_t)ctx->max_lds || R.lds_c > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "pcl_rollout_dev: the large-generator rollout needs %zu B of LDS (> %d) for n = %d, m = %d", std::max(R.lds_e, R.lds_c), ctx->max_lds, p.n, p.m);
+    if (items * R.P > 0x7fffffffLL || (long long)p.batch * R.S > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    p.LD = R.LD;
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_large_expm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.lds_e));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_large_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.lds_c));
+    p.nc = R.npc;
+    p.S = R.P;
+    p.lds_doubles = (int)(R.lds_e / sizeof(double));
+    if (ctx->opt_large_rollout_stage != 2) {
+        hipLaunchKernelGGL(pcl_large_expm_kernel, dim3((unsigned)(items * R.P)), dim3((unsigned)R.threads), R.lds_e, ctx->stream, p);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    ctx->last_kernel = 270;  // the large family's rollout (280 + q: its residual, 290 + q: residual + Jacobian)
+    ctx->last_n_stream = 0;
+    if (ctx->opt_large_rollout_stage == 1) return PCL_OK;
+    p.nc = R.nc;
+    p.S = R.S;
+    p.lds_doubles = (int)(R.lds_c / sizeof(double));
+    hipLaunchKernelGGL(pcl_large_chain_kernel, dim3((unsigned)((long long)p.batch * R.S)), dim3((unsigned)R.threads), R.lds_c, ctx->stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    return PCL_OK;
+}
+
 extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_rollout_dev");
+    LARGE_FULL_GATE(ctx, "pcl_rollout_dev");
     VAR_GATE(ctx, "pcl_rollout_dev");
     if (ctx->var) return var_rollout_dev(ctx, Z, X_out);
+    if (ctx->large) return launch_large_rollout(ctx, Z, X_out);
     ON_DEVICE(ctx);
     KParams p;
     fill_params(ctx, p);
@@ -2852,7 +2935,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
 extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_rollout");
+    LARGE_FULL_GATE(ctx, "pcl_rollout");
     VAR_GATE(ctx, "pcl_rollout");
     ON_DEVICE(ctx);
     const long long nv = (long long)ctx->win_count * ctx->desc.N * ctx->x_dim;

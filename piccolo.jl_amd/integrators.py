@@ -92,13 +92,27 @@ def _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode=
         raise ValueError("large_hessian=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
 
 
+def _check_large_full(large_full, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_full`` (the library's option of that name: the objective family and the rollout at generator dimensions 66 .. 128) goes
+    with ``large_generator=True`` on the Pade constraint of a plain context: anything else is a ``ValueError``, before any device call."""
+    if not large_full:
+        return
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("large_full=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)")
+    if not large_generator:
+        raise ValueError("large_full=True is the objective and the rollout of a context created with large_generator=True: it needs that keyword")
+    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP:
+        raise ValueError("large_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
-                 large_generator=False, large_hessian=False):  # fmt: skip
+                 large_generator=False, large_hessian=False, large_full=False):  # fmt: skip
         _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
+        _check_large_full(large_full, large_generator, pade_order, batch_mode)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order, batch_mode)
@@ -148,10 +162,12 @@ class _PclContext:
         self.hess_nnz = self.hess_per = 0
         self.compact_nnz = self.compact_per = 0
         # ``large_generator`` (the flag PCL_LARGE_N) at a generator dimension above 64: residual and Jacobian only -- the Hessian of the Lagrangian,
-        # the compact Jacobian, the merit / reduce payload, the rollout and the objective raise with the library's message.  At n <= 64 the
+        # the compact Jacobian, the merit / reduce payload, the rollout and the objective raise with the library's message (the rollout and the
+        # objective unless ``large_full`` switches the library's option of that name on).  At n <= 64 the
         # flag changes nothing.  ``large_hessian`` switches the library's option large_hess on there: hess_nnz / hess_per follow it (set_option)
         self.large = bool(large_generator) and n > 64
         self.large_hessian = False
+        self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
         if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
             self.set_option("var_exp_hess_tiles", 1)
         if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
@@ -165,6 +181,8 @@ class _PclContext:
             self.hess_nnz, self.hess_per = a.value, b.value
         if exp_full:
             self.set_option("exp_full", 1)
+        if large_full and self.large:  # (at n <= 64 the ordinary context serves objective and rollout as always: the option is not set)
+            self.set_option("large_full", 1)
         if var_compact:
             self.set_option("var_compact", 1)
         # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
@@ -496,6 +514,8 @@ class _PclContext:
             if self.large_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
+        if self.large and key == "large_full":
+            self.large_full = bool(value)
         if key == "var_compact" and self.batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):  # ... the stacked state's compact Jacobian
             self.var_compact = bool(value)
             a, b = ctypes.c_int64(), ctypes.c_int64()
@@ -564,7 +584,7 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False):
+                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -579,12 +599,16 @@ class HipPadeIntegrator:
         ``var_compact`` belongs to the variational constructors: ``True`` here is a ``ValueError``.
         ``large_generator=True`` sets the library's flag ``PCL_LARGE_N``: generator dimensions 66 .. 128 (a transmon with a cavity, density vectors of
         9 .. 11 levels) on the Pade constraint, residual and Jacobian only -- ``hessian_structure`` / ``eval_hessian_of_lagrangian``, the rollout and the
-        objective raise; solve with a quasi-Newton Hessian.  Never set on its own: without it such a system is refused as before.  With
+        objective raise (see ``large_hessian`` and ``large_full`` below); solve with a quasi-Newton Hessian.  Never set on its own: without it such a system is refused as before.  With
         ``pade_order="exp"`` the library refuses it.  At a dimension up to 64 it changes nothing.
         ``large_hessian=True`` (with ``large_generator=True`` on the Pade constraint only, else ``ValueError``): the Hessian of the Lagrangian is served at
         those dimensions too (the library's option ``large_hess``) -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work.  At a dimension up to
-        64 the ordinary context serves its Hessian as always."""
+        64 the ordinary context serves its Hessian as always.
+        ``large_full=True`` (the same conditions, else ``ValueError``): the objective family -- goals, weights, regularisers, value, gradient and the
+        objective's Hessian -- and the rollout are served at those dimensions too (the library's option ``large_full``): ``rollout``, ``rollout_dev``
+        and ``Objective.bind`` work unchanged.  Independent of ``large_hessian``; at a dimension up to 64 the ordinary context serves them as always."""
         _check_large_hessian(large_hessian, large_generator, pade_order)
+        _check_large_full(large_full, large_generator, pade_order)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order)
         _check_var_compact(var_compact)
@@ -628,7 +652,7 @@ class HipPadeIntegrator:
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
             state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
-            large_hessian=large_hessian,
+            large_hessian=large_hessian, large_full=large_full,
         )  # fmt: skip
         self._large_generator = bool(large_generator)
         if pade_order == 0:
@@ -692,8 +716,9 @@ class HipVariationalIntegrator:
     path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False):
+                 var_compact=False, large_hessian=False, large_full=False):
         _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
+        _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
         exp_hessian = _exp_hessian_value(exp_hessian)
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))

@@ -86,7 +86,13 @@ end
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
                       exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
-                      large_hessian::Bool = false)
+                      large_hessian::Bool = false, large_full::Bool = false)
+    # large_full = true (the same conditions): the library's option large_full -- goals, weights, regularisers, pcl_objective*, pcl_objective_hess*
+    # and pcl_rollout* are served at those dimensions too.  Independent of large_hessian; at n <= 64 the ordinary context serves them as always.
+    (large_full && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_full = true is the objective and the rollout of a context created with large_generator = true: it needs that keyword"))
+    (large_full && pade_order == PCL_ORDER_EXP) &&
+        throw(ArgumentError("HipPadeIntegrator: large_full = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large contexts"))
     # large_hessian = true (with large_generator = true on the Pade constraint only): the library's option large_hess -- the Hessian of the
     # Lagrangian at those dimensions too (hess_per > 0, eval_hessian = true works).  At n <= 64 the ordinary context serves its Hessian as always.
     (large_hessian && !large_generator) &&
@@ -125,6 +131,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     # (exp_full: the library's option of that name -- the host-pointer calls below then move the compact values over PCIe and expand on the host)
     exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
     (large && large_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_hess", 1))
+    (large && large_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_full", 1))
     ((pade_order == PCL_ORDER_EXP && !exp_hessian) || (large && !large_hessian)) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
@@ -193,7 +200,7 @@ end
 # the compact path (one -E per interval over PCIe, replicated by the host's threads) with the bits of the full path, and the compact /
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
-const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true
+const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -293,7 +300,8 @@ end
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false, large_hessian::Bool = false)
+                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false)
+    large_full && throw(ArgumentError("HipPadeIntegrator: large_full = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)"))
     large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
