@@ -71,13 +71,7 @@ extern "C" int pcl_reduce_sum(pcl_ctx *ctx, double *buf, int64_t n) {  // host b
     if (!ctx->comm) return fail(ctx, PCL_ERCCL, "pcl_reduce_sum: call pcl_comm_init first");
     if (n == 0) return PCL_OK;
     ON_DEVICE(ctx);
-    if (ctx->reduce_cap < n) {
-        if (ctx->dreduce) (void)hipFree(ctx->dreduce);
-        ctx->dreduce = nullptr;
-        ctx->reduce_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dreduce, (size_t)n * sizeof(double)));
-        ctx->reduce_cap = n;
-    }
+    if (int rc = grow_scratch(ctx, &ctx->reduce_cap, n, &ctx->dreduce, (size_t)n)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->dreduce, buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (int rc = pcl_reduce_sum_dev(ctx, ctx->dreduce, n)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(buf, ctx->dreduce, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -151,6 +151,21 @@ bool slurp(const std::string &path, std::string &out) {
     return !out.empty();
 }
 
+// the kernel headers next to the library that every run-time compilation sees (their texts enter the cache key, in this order)
+constexpr int kJitNH = 11;
+const char *const kJitHeaders[kJitNH] = {"pcl_device_common.hpp", "pcl_kernels_fused_v2.hpp", "pcl_kernel_fused_v3.hpp", "pcl_kernels_hessian.hpp",
+                                         "pcl_kernel_hessian_v3.hpp", "pcl_kernel_hessian_sparse.hpp", "pcl_kernel_eval_sparse.hpp",
+                                         "pcl_kernel_fused_sparse.hpp", "pcl_kernel_hess_sparse4.hpp", "pcl_kernel_hess_cols.hpp", "pcl_kernel_hess_cols_parts.hpp"};
+bool jit_read_headers(const std::string &dir, std::string *hdr, const char **hdrp, std::string &err) {
+    for (int i = 0; i < kJitNH; ++i) {
+        if (!slurp(dir + "/" + kJitHeaders[i], hdr[i])) {
+            err = "kernel header not found next to the library: " + dir + "/" + kJitHeaders[i];
+            return false;
+        }
+        hdrp[i] = hdr[i].c_str();
+    }
+    return true;
+}
 
 void mkdir_p(const std::string &dir) {  // (the leaf -- the cache itself -- for this user only)
     for (size_t i = 1; i <= dir.size(); ++i)
@@ -282,22 +297,12 @@ hipFunction_t jit_compile(int device, const std::string &key_, const std::string
     std::string dir(info.dli_fname);
     const size_t slash = dir.find_last_of('/');
     dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
-    const char *names[] = {"pcl_device_common.hpp", "pcl_kernels_fused_v2.hpp", "pcl_kernel_fused_v3.hpp", "pcl_kernels_hessian.hpp",
-                           "pcl_kernel_hessian_v3.hpp", "pcl_kernel_hessian_sparse.hpp", "pcl_kernel_eval_sparse.hpp",
-                           "pcl_kernel_fused_sparse.hpp", "pcl_kernel_hess_sparse4.hpp", "pcl_kernel_hess_cols.hpp", "pcl_kernel_hess_cols_parts.hpp"};
-    constexpr int NH = 11;
-    std::string hdr[NH];
-    const char *hdrp[NH];
-    for (int i = 0; i < NH; ++i) {
-        if (!slurp(dir + "/" + names[i], hdr[i])) {
-            g_jit_note = "kernel header not found next to the library: " + dir + "/" + names[i];
-            return nullptr;
-        }
-        hdrp[i] = hdr[i].c_str();
-    }
+    std::string hdr[kJitNH];
+    const char *hdrp[kJitNH];
+    if (!jit_read_headers(dir, hdr, hdrp, g_jit_note)) return nullptr;
     std::vector<char> code;
     std::string lname = plain_name ? std::string(name_expr) : std::string();
-    const std::string ckey = jit_cache_key(source, hdr, NH, plain_name ? "" : name_expr);
+    const std::string ckey = jit_cache_key(source, hdr, kJitNH, plain_name ? "" : name_expr);
     bool from_cache = false;
     std::string cache_file;  // the user-cache file the module came from (removed if it turns out not to load)
     const std::string ucd = cache_enabled() ? user_cache_dir() : std::string();
@@ -334,7 +339,7 @@ hipFunction_t jit_compile(int device, const std::string &key_, const std::string
     }
     if (!loaded) {
         if (!rtc_load()) return nullptr;
-        if (!rtc_compile(source, hdrp, names, NH, name_expr, plain_name, key_, code, lname)) return nullptr;
+        if (!rtc_compile(source, hdrp, kJitHeaders, kJitNH, name_expr, plain_name, key_, code, lname)) return nullptr;
         if (!ucd.empty()) {
             mkdir_p(ucd);
             if (user_cache_trusted(ucd)) (void)write_file_atomic(ucd, ckey + ".hsaco", pack_module(code, lname));
@@ -404,20 +409,10 @@ static int prebuild_source(const std::string &source, const char *name_expr, con
     std::string dir(info.dli_fname);
     const size_t slash = dir.find_last_of('/');
     dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
-    const char *names[] = {"pcl_device_common.hpp", "pcl_kernels_fused_v2.hpp", "pcl_kernel_fused_v3.hpp", "pcl_kernels_hessian.hpp",
-                           "pcl_kernel_hessian_v3.hpp", "pcl_kernel_hessian_sparse.hpp", "pcl_kernel_eval_sparse.hpp",
-                           "pcl_kernel_fused_sparse.hpp", "pcl_kernel_hess_sparse4.hpp", "pcl_kernel_hess_cols.hpp", "pcl_kernel_hess_cols_parts.hpp"};
-    constexpr int NH = 11;
-    std::string hdr[NH];
-    const char *hdrp[NH];
-    for (int i = 0; i < NH; ++i) {
-        if (!slurp(dir + "/" + names[i], hdr[i])) {
-            err = "kernel header not found next to the library: " + dir + "/" + names[i];
-            return PCL_EHIP;
-        }
-        hdrp[i] = hdr[i].c_str();
-    }
-    const std::string ckey = jit_cache_key(source, hdr, NH, "");
+    std::string hdr[kJitNH];
+    const char *hdrp[kJitNH];
+    if (!jit_read_headers(dir, hdr, hdrp, err)) return PCL_EHIP;
+    const std::string ckey = jit_cache_key(source, hdr, kJitNH, "");
     const std::string odir = out_dir && out_dir[0] ? std::string(out_dir) : dir + "/prebuilt";
     std::vector<char> blob;
     {
@@ -431,7 +426,7 @@ static int prebuild_source(const std::string &source, const char *name_expr, con
     }
     std::vector<char> code;
     std::string lname;
-    if (!rtc_compile(source, hdrp, names, NH, name_expr, true, "prebuild", code, lname)) {
+    if (!rtc_compile(source, hdrp, kJitHeaders, kJitNH, name_expr, true, "prebuild", code, lname)) {
         err = g_jit_note;
         return PCL_EHIP;
     }

@@ -410,15 +410,10 @@ static int launch_exp_merit(pcl_ctx *ctx, const double *Z, const double *lam, do
         return fail(ctx, PCL_ESHAPE, "pcl_eval_jac_merit_dev: the adjoint chain kernel needs %zu B of LDS (> %d) for n=%d: four n x n tiles of %zu B", std::max(lds, lds_prep),
                     ctx->max_lds, p.n, tile * sizeof(double));
     const long long items = (long long)p.batch * p.K;
-    if (items > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "too many work items");
+    if (int rc = check_grid(ctx, items)) return rc;
     TRY(merit_scratch(ctx));
     const long long cap = items * (2LL * p.n * p.n + 2);  // (the workspace of the Hessian launches: the same layout, the same stream)
-    if (ctx->exph_cap < cap) {
-        if (ctx->dexph) (void)hipFree(ctx->dexph);
-        ctx->dexph = nullptr, ctx->exph_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dexph, (size_t)cap * sizeof(double)));
-        ctx->exph_cap = cap;
-    }
+    if (int rc = grow_scratch(ctx, &ctx->exph_cap, cap, &ctx->dexph, (size_t)cap)) return rc;
     TRY(launch_exp(ctx, p, false));
     p.mu = lam ? lam : delta;
     HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_exp_hess_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));

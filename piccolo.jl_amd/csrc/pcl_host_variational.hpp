@@ -387,12 +387,7 @@ static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *
     const long long grid = (long long)ctx->K * v * (jac ? std::max(m, 1) : 1);
     if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
     const long long cap = (long long)ctx->K * ((long long)nn + 2);
-    if (ctx->exph_cap < cap) {
-        if (ctx->dexph) (void)hipFree(ctx->dexph);
-        ctx->dexph = nullptr, ctx->exph_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dexph, (size_t)cap * sizeof(double)));
-        ctx->exph_cap = cap;
-    }
+    if (int rc = grow_scratch(ctx, &ctx->exph_cap, cap, &ctx->dexph, (size_t)cap)) return rc;
     p.Z = Z;
     p.delta = delta;
     p.vals = vals;
@@ -426,7 +421,6 @@ static int var_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *
 
 // The Hessian of the Lagrangian of PCL_BATCH_VARIATIONAL_EXP (option var_exp_hess; pcl_kernel_var_exp_hess.hpp).  The octuple kernel rotates nine
 // n x LD tiles (eight and the scratch) and G(u_k) takes a tenth where that fits; the quadruple kernel five, a sixth, and its reduction words.
-static int lds_ld(int n);
 static size_t var_exp_hess_tile_bytes(const pcl_ctx *ctx) { return (size_t)lds_ld(ctx->n) * ctx->n * sizeof(double); }
 static size_t var_exp_hess_lds_bytes(const pcl_ctx *ctx, bool oct, int *g_lds) {
     const size_t tile = var_exp_hess_tile_bytes(ctx), base = oct ? 9 * tile : 5 * tile + 16 * sizeof(double);

@@ -66,7 +66,7 @@ VAR_HESS_LDS = ("V1", "V2", "V3")  # nine LDS tiles fit
 VAR_HESS_WS = ("V4", "V6")  # served by var_exp_hess_tiles = 1
 
 
-# ---- LDS arithmetic of the launch code (piccolo_hip.hip launch_exp / exp_hess_lds_bytes, pcl_host_variational.hpp) ---------------------------
+# ---- LDS arithmetic of the launch code (pcl_host_launch_pade.hpp launch_exp, pcl_host_launch_hess.hpp exp_hess_lds_bytes, pcl_host_variational.hpp) ---------------------------
 def lds_ld(n):
     return ((n + 3) & ~3) + 2
 

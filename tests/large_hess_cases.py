@@ -5,7 +5,7 @@ The cases, N = 4, the knots and the three steps are those of tests/large_shape_c
 are np.random.default_rng(15000 + 17 index + 77 + member).standard_normal (vector_shape_cases.rand_mu does not know the L names); the truth is
 vector_shape_cases.truth_values(..., mu, order, hessian=True)[2] in np.longdouble, computed once per (case, order, seed, drift, member).
 
-The launch code's plan (large_hess_plan in piccolo_hip.hip, restated below as `hess_plan`): beside the one n x n tile (LD = n | 1) a unit of nc
+The launch code's plan (large_hess_plan in pcl_host_launch_hess.hpp, restated below as `hess_plan`): beside the one n x n tile (LD = n | 1) a unit of nc
 state columns and mg drives holds nc (10 + 4 mg) column blocks of LD doubles and nc (mg (m + 1) + 1) partial sums; the widest nc that leaves
 room for one drive, then the most drives that fit, slices and groups evened.  What it gives per case (U units = workgroups per interval,
 sx slices of nc columns x ngrp groups of mg drives, LDS bytes):
@@ -45,7 +45,7 @@ TABLE = {
 }  # fmt: skip
 
 
-# ---- the launch code's arithmetic (large_hess_plan, piccolo_hip.hip) -------------------------------------------------------------------------
+# ---- the launch code's arithmetic (large_hess_plan, pcl_host_launch_hess.hpp) -------------------------------------------------------------------------
 def hess_lds_bytes(n, m, nc, mg):
     LD = n | 1
     return (LD * n + LD * nc * (10 + 4 * mg) + SLACK + m + 8 + nc * (mg * (m + 1) + 1)) * 8

@@ -1,5 +1,5 @@
 """Cases for generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N; piccolo.jl_amd/csrc/pcl_kernel_pade_large.hpp), at the sizes at
-which the launch code's plan (large_plan in piccolo_hip.hip, restated below) and the kernel branch; importable without a GPU.
+which the launch code's plan (large_plan in pcl_host_launch_pade.hpp, restated below) and the kernel branch; importable without a GPU.
 
 The knot, N = 4 and the three steps per case are those of tests/vector_shape_cases.py -- [X | dt | t | u], u ~ 0.4 N(0, 1); interval 0 at
 h |G|_2 = 0.15, interval 1 at -0.3, interval 2 at the smallest of vc.LONG_STEPS at which zeroing c_5 of order 10 moves the residual by 1e-7 of
@@ -55,7 +55,7 @@ TABLE = {
 }  # fmt: skip
 
 
-# ---- the launch code's arithmetic (large_plan, piccolo_hip.hip) -----------------------------------------------------------------------------
+# ---- the launch code's arithmetic (large_plan, pcl_host_launch_pade.hpp) -----------------------------------------------------------------------------
 def large_plan(n, cols, m, jac=True, items=N - 1, n_cu=256, cols_per_slice=0, slices=0):
     LD, threads = n | 1, 64 * ((n + 15) // 16)
     fixed = LD * n + SLACK + m + 8

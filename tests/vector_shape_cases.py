@@ -1,5 +1,5 @@
 """Cases that walk the Pade kernels over the states that are not a square unitary -- kets, multi-ket states and density vectors -- at the
-sizes at which the launch code (piccolo.jl_amd/csrc/piccolo_hip.hip) and the kernels branch; importable without a GPU.
+sizes at which the launch code (piccolo.jl_amd/csrc/pcl_host_launch_pade.hpp, pcl_host_launch_hess.hpp) and the kernels branch; importable without a GPU.
 
 Generators are random and dense, so that edge rows, edge columns and the last k steps of every product carry weight:
     iso    G(H) of a dense complex Hermitian H (ket or multi-ket state, n = 2 d); K5 alone takes po.config_system(3)'s generators
@@ -74,7 +74,7 @@ EVEN = tuple(c for c in CASES if CASES[c][1] % 2 == 0)
 RESEED = {}
 
 
-# ---- the launch code's arithmetic (piccolo_hip.hip) ------------------------------------------------------------------------------------------
+# ---- the launch code's arithmetic (pcl_host_launch_*.hpp) ------------------------------------------------------------------------------------------
 def lds_ld(n):
     return ((n + 3) & ~3) + 2
 
