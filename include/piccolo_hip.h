@@ -208,10 +208,12 @@ typedef enum pcl_status {
  * shared or per-member G0, both batch modes, the member window, 1 .. d state columns and m = 0 .. 24 drives; values, order and layout are those
  * of every other Pade context.  Every work split gives the same bits and two launches give the same bits (no atomics).
  * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
- * (host-pointer calls deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*, and pade_order = 0 with
+ * (host-pointer calls deliver full values unless the option "large_reduce" is on: below), pcl_set_member_window, streams and sync, options,
+ * pcl_deriv_*, and pade_order = 0 with
  * pcl_set_order_policy / pcl_set_order_from_trajectory.  PCL_ENOTIMPL, each message naming PCL_LARGE_N: pcl_hess[_dev], pcl_hess_nnz,
- * pcl_hess_structure[_i64] (unless the option "large_hess" is on: below), the compact Jacobian trio, the merit /
- * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev), and -- unless the
+ * pcl_hess_structure[_i64] (unless the option "large_hess" is on: below), the compact Jacobian trio and the merit /
+ * reduce entry points (pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev, pcl_eval_jac_merit_objective_dev; unless the option
+ * "large_reduce" is on: below), and -- unless the
  * option "large_full" is on: below -- pcl_rollout[_dev] and the objective family (goals, weights, regularisers, pcl_infidelity_dev,
  * pcl_objective[_dev], pcl_objective_hess_*).
  * The Hessian of the Lagrangian: pcl_set_option "large_hess" = 1 (0 by default, never on by itself; PCL_EINVAL on a context that is not large)
@@ -229,10 +231,22 @@ typedef enum pcl_status {
  * plan (pcl_kernel_large_rollout.hpp: propagators by column panels as a substepped degree-18 Taylor polynomial, then the chain of the knots; no
  * atomics, every work split bitwise equal); its workspace (batch x (N - 1) x n^2 doubles) is allocated at the first rollout.
  * Back at 0 the refusals return and goal, weights and regularisers are dropped.
+ * The compact Jacobian and the reduce payload: pcl_set_option "large_reduce" = 1 (0 by default, never on by itself; PCL_EINVAL on a context that
+ * is not large, and for any value outside 0 and 1; independent of the other two) makes pcl_jac_compact_nnz, pcl_eval_jac_compact_dev,
+ * pcl_jac_expand_dev, pcl_merit_grad_len, pcl_merit_grad_dev and pcl_eval_jac_merit_dev serve a large context with the contracts of n <= 64:
+ * the compact layout [-B+ (n^2) | B- (n^2) | tails] per interval (one state column: the full layout), the member window on the compact trio, every
+ * member on the merit entry points.  pcl_eval_jac_merit_dev accepts vals = NULL there: delta and the payload alone, chain units only, no Jacobian
+ * value formed or written.  pcl_eval_jac_merit_objective_dev needs "large_full" = 1 as well (and a unitary goal); with "large_reduce" alone it
+ * stays refused in the same words.  Member weights are the objective family's: pcl_set_weights is served by "large_full".  The host-pointer
+ * calls then take the compact route (compact values over PCIe, expanded by the host's threads) when the state has more than one column and
+ * "host_path" is not 1.  Modes of the one kernel family (pcl_kernel_pade_large.hpp) and pcl_expand_large_kernel; the compact values have the bits
+ * of the full launch's, the expansion the bits of pcl_eval_jac_dev, and the payload of the fused launch the bits of the payload-only launch under
+ * every work split (no atomics).  Back at 0 the refusals return.
  * Options: "cols_per_slice" caps the state columns per workgroup (Jacobian, Hessian and the rollout's chain), "general_slices" sets the least
  * number of workgroups per interval of the Jacobian launch and of the rollout's propagator launch, "large_hess_drives" caps the drives per workgroup of the Hessian launch (0 auto; PCL_EINVAL when negative or
  * off a large context); "kernel_version", "general_kernel_version", "general_threads", "use_mfma", "hess_kernel", "nt" = 2 have no effect.
- * get_option "last_kernel" reads 290 + q after a Jacobian launch, 280 + q after a residual-only launch and 270 after a rollout,
+ * get_option "last_kernel" reads 290 + q after a Jacobian launch (with or without the payload's partial sums), 300 + q after a compact launch,
+ * 310 + q after a payload-only launch, 280 + q after a residual-only launch and 270 after a rollout,
  * "last_hess_kernel" 290 + q after a Hessian launch (q = pade_order / 2). */
 #define PCL_LARGE_N 0x100
 #define PCL_LARGE_MAX_N 128

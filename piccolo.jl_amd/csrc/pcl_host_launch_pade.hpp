@@ -180,11 +180,12 @@ static int launch_pade_v2(pcl_ctx *ctx, KParams &p) {
 // then units are added until the panel of ceil(n / U) power columns fits beside the chain blocks and a thread owns at most PL_NP pairs of it,
 // and, for launches of few intervals, up to one unit per 16 power columns while the grid stays within one round of the CUs (option
 // general_slices: that many units at least).  Every split gives the same bits.
+// The payload-only launch (option large_reduce, pcl_eval_jac_merit_dev without values): the same chain units and nothing else -- U = sx ngrp, npc = 0.
 struct LargePlan {
     int LD, threads, NB, sx, nc, mg, ngrp, U, npc;
     size_t lds;
 };
-static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargePlan &P) {
+static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargePlan &P, bool payload_only = false) {
     P.LD = n | 1;
     P.threads = 64 * ((n + 15) / 16);
     const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
@@ -210,7 +211,7 @@ static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, lon
     const int chain_units = P.sx * P.ngrp, chain_blocks = P.nc * (jac ? 2 + 2 * (2 + P.mg) : 4);
     P.U = chain_units;
     P.npc = 0;
-    if (jac) {
+    if (jac && !payload_only) {
         auto fits = [&](int U) {
             const int npc = (n + U - 1) / U;
             return chain_blocks + npc <= P.NB && ((long long)n * npc + 1) / 2 <= (long long)PL_NP * P.threads;
@@ -224,11 +225,12 @@ static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, lon
     }
     P.lds = (size_t)(fixed + (long long)P.LD * (chain_blocks + P.npc)) * sizeof(double);
 }
-static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac) {
+// mode (option large_reduce): PL_FULL | PL_COMPACT | PL_MERIT (p.mpart, p.mlam set) | PL_PAYLOAD (the same, no values) -- pcl_kernel_pade_large.hpp
+static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac, int mode = PL_FULL) {
     fill_pade(p, ctx->desc.pade_order);
     LargePlan P;
     const long long items = (long long)p.batch * p.K;
-    large_plan(ctx, p.n, p.cols, p.m, want_jac, items, P);
+    large_plan(ctx, p.n, p.cols, p.m, want_jac, items, P, mode == PL_PAYLOAD);
     if (P.lds > (size_t)ctx->max_lds)
         return fail(ctx, PCL_ESHAPE, "the large-generator kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
     p.LD = P.LD;
@@ -239,11 +241,16 @@ static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac) {
     const long long grid = items * P.U;
     if (int rc = check_grid(ctx, grid)) return rc;
     typedef void (*kern_t)(const KParams, const int, const int, const int);
-    const kern_t kern = want_jac ? (kern_t)pcl_pade_large_kernel<true> : (kern_t)pcl_pade_large_kernel<false>;
+    const kern_t kern = !want_jac             ? (kern_t)pcl_pade_large_kernel<false>
+                        : mode == PL_COMPACT  ? (kern_t)pcl_pade_large_kernel<true, PL_COMPACT>
+                        : mode == PL_MERIT    ? (kern_t)pcl_pade_large_kernel<true, PL_MERIT>
+                        : mode == PL_PAYLOAD  ? (kern_t)pcl_pade_large_kernel<true, PL_PAYLOAD>
+                                              : (kern_t)pcl_pade_large_kernel<true>;
     if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 7 : 8, P.lds)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg, P.npc);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->last_kernel = (want_jac ? 290 : 280) + p.q;
+    // 280 + q the residual | 290 + q residual + Jacobian (with or without the payload's partial sums) | 300 + q the compact values | 310 + q the payload alone
+    ctx->last_kernel = (!want_jac ? 280 : mode == PL_COMPACT ? 300 : mode == PL_PAYLOAD ? 310 : 290) + p.q;
     ctx->last_n_stream = 0;
     return PCL_OK;
 }
@@ -781,7 +788,16 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
     if (ctx->large) {
-        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context created with PCL_LARGE_N");
+        if (compact && !ctx->large_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context created with PCL_LARGE_N");
+        if (want_jac && compact) return launch_pade_large(ctx, p, true, PL_COMPACT);
+        // the payload-fused call (pcl_eval_jac_merit_dev, option large_reduce): every member, so that the partial sums are numbered as the finish kernel reads them
+        if (want_jac && ctx->large_reduce && merit_call(ctx, p)) {
+            if (!ctx->dmcols) HIP_TRY(ctx, hipMalloc((void **)&ctx->dmcols, (size_t)ctx->desc.batch * p.K * p.cols * (p.m + 2) * sizeof(double)));
+            p.mpart = ctx->dmcols;
+            p.mlam = ctx->merit_lam;
+            ctx->merit_fused = 1;
+            return launch_pade_large(ctx, p, true, PL_MERIT);
+        }
         return launch_pade_large(ctx, p, want_jac);
     }
     if (ctx->exp) return launch_fused_exp(ctx, p);

@@ -427,9 +427,32 @@ static int launch_exp_merit(pcl_ctx *ctx, const double *Z, const double *lam, do
     ctx->last_kernel = 103;  // the adjoint payload launch
     return merit_sum(ctx, out);
 }
+static int launch_merit_finish(pcl_ctx *ctx, double *out);
+// The payload of a large context without its Jacobian (option large_reduce; mode PL_PAYLOAD of pcl_kernel_pade_large.hpp): chain units only, the
+// residual and the partial sums per state column, then the finish kernel.  Every member, whatever the member window says.
+static int launch_large_payload(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *out) {
+    ON_DEVICE(ctx);
+    if (int rc = check_device_error(ctx, "pcl_eval_jac_merit_dev")) return rc;
+    if (int rc = resolve_order(ctx, nullptr, "pcl_eval_jac_merit_dev")) return rc;
+    const pcl_desc &D = ctx->desc;
+    const int wf = ctx->win_first, wc = ctx->win_count;
+    ctx->win_first = 0, ctx->win_count = D.batch;
+    KParams p;
+    fill_params(ctx, p);
+    ctx->win_first = wf, ctx->win_count = wc;
+    p.Z = Z;
+    p.delta = delta;
+    p.jac = nullptr;
+    p.jac_per = 0;
+    if (!ctx->dmcols) HIP_TRY(ctx, hipMalloc((void **)&ctx->dmcols, (size_t)D.batch * p.K * p.cols * (p.m + 2) * sizeof(double)));
+    p.mpart = ctx->dmcols;
+    p.mlam = lam;
+    TRY(launch_pade_large(ctx, p, true, PL_PAYLOAD));
+    return launch_merit_finish(ctx, out);
+}
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
-    LARGE_NOTIMPL(ctx, "pcl_merit_grad_dev");
+    LARGE_REDUCE_GATE(ctx, "pcl_merit_grad_dev");
     VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
     EXP_FULL_GATE(ctx, "pcl_merit_grad_dev");
     if (!ctx) return PCL_EINVAL;
@@ -447,8 +470,12 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 }
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
-    LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
+    LARGE_REDUCE_GATE(ctx, "pcl_eval_jac_merit_dev");
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
+    if (ctx && ctx->large && Z && delta && out && !vals) {  // the payload alone: no Jacobian value is formed (vals may be NULL under large_reduce)
+        ctx->merit_fused = 0;
+        return launch_large_payload(ctx, Z, lam, delta, out);
+    }
     if (ctx && ctx->exp && !ctx->exp_full && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_dev");
     if (!ctx) return PCL_EINVAL;
@@ -467,6 +494,10 @@ extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const doubl
     if (!ctx->merit_fused) return pcl_merit_grad_dev(ctx, delta, lam, vals, out);  // other kernels / member windows: the separate payload kernels
     ON_DEVICE(ctx);
     if (ctx->exp) return merit_sum(ctx, out);  // (the exponential kernel left the sums per (member, interval): nothing to add over columns)
+    return launch_merit_finish(ctx, out);
+}
+// the payload from the partial sums per state column in ctx->dmcols (the fused kernels leave them): ONE launch
+static int launch_merit_finish(pcl_ctx *ctx, double *out) {
     const pcl_desc &D = ctx->desc;
     const bool traj = D.batch_mode == PCL_BATCH_TRAJ;
     const int sets = traj ? D.batch : 1;
@@ -513,6 +544,15 @@ static int obj_hess_alloc(pcl_ctx *ctx, double **buf, long long count, const cha
     *buf = nullptr;
     (void)hipGetLastError();
     return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "%s (%lld doubles): %s", what, count, hipGetErrorString(e));
+}
+// option large_reduce (large contexts): 1 serves the compact Jacobian trio, the host-pointer calls' compact route and the merit / reduce entry points;
+// 0 refuses them again.  Never on by itself; any other context refuses 1 and reads 0
+static int large_set_reduce(pcl_ctx *ctx, int64_t on) {
+    if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "large_reduce must be 0 or 1");
+    if (on && !ctx->large)
+        return fail(ctx, PCL_EINVAL, "large_reduce = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64, on the Pade constraint); every other context serves its compact Jacobian and reduce payload without it or by an option of its own");
+    ctx->large_reduce = (int)on;
+    return PCL_OK;
 }
 // option large_full (large contexts): 1 serves the objective family and the rollout; 0 refuses them again and drops goal, weights and regularisers
 static int large_set_full(pcl_ctx *ctx, int64_t on) {
@@ -714,7 +754,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 // regulariser rows, the terminal infidelities and the payload's finish (pcl_ens_tail_kernel); the same bits as the separate calls.
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
-    LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
+    if (ctx && !(ctx->large_reduce && ctx->large_full)) LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");  // (a large context: both options)
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;
@@ -745,7 +785,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
     return PCL_OK;
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
-    LARGE_NOTIMPL(ctx, "pcl_merit_grad_len");
+    LARGE_REDUCE_GATE(ctx, "pcl_merit_grad_len");
     VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
     EXP_FULL_GATE(ctx, "pcl_merit_grad_len");
     if (!ctx) return PCL_EINVAL;

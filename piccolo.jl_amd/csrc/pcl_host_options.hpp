@@ -62,6 +62,9 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     else if (!strcmp(key, "large_full")) {  // large contexts: serve the objective family and the rollout (0: refuse them, the default, and drop goal, weights, regularisers)
         TRY(large_set_full(ctx, v));
     }
+    else if (!strcmp(key, "large_reduce")) {  // large contexts: serve the compact Jacobian trio, the host calls' compact route and the merit / reduce payload (0: refuse them, the default)
+        TRY(large_set_reduce(ctx, v));
+    }
     else if (!strcmp(key, "large_rollout_stage")) {  // ... measurements (bench/bench_large_full.py): 0 both launches of the rollout | 1 the propagators only | 2 the chain only
         if (v < 0 || v > 2 || !ctx->large) return fail(ctx, PCL_EINVAL, "large_rollout_stage must be 0, 1 or 2, on a large context (PCL_LARGE_N, generator dimension above 64)");
         ctx->opt_large_rollout_stage = v;
@@ -220,6 +223,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->opt_large_hess_drives;
     else if (!strcmp(key, "large_full"))
         *v = ctx->large_full;
+    else if (!strcmp(key, "large_reduce"))
+        *v = ctx->large_reduce;
     else if (!strcmp(key, "large_rollout_stage"))
         *v = ctx->opt_large_rollout_stage;
     else if (!strcmp(key, "host_threads"))

@@ -18,12 +18,22 @@
 // Every element of every output is formed by one fixed sequence of operations whatever the split (sx, mg, npc): the k order of the products
 // is fixed, the additive terms are explicit fused multiply-adds, and no sum crosses a unit -- no atomics, and every split gives the same bits.
 // The drives' ELL rows are read from memory (L2): at m = 24, n = 120 they are 69 KB.
+//
+// MODE (option large_reduce; the plain launch is PL_FULL, the code it had before the modes):
+//   PL_COMPACT  the compact Jacobian [-B+ | B- | tails]: every unit stores its panel once instead of `cols` times; the same registers, the same bits;
+//   PL_MERIT    the full values and, once the level loop has ended, the reduce payload's partial sums: a chain unit (slice s, group g) forms, per
+//               state column of its slice, <d delta / d u_l, lam> for each of its drives, and group 0 also <d delta / d dt, lam> and <lam, delta>
+//               (times 1/2 when lam = delta) -- one wave per (column, job), lane-strided over the n rows, then the shuffle tree: the order of the
+//               additions depends on n alone.  Plain stores into p.mpart[((b K + k) cols + c)(m + 2) + l], which pcl_merit_finish_kernel reads;
+//               exactly one unit owns each (c, l): no atomics, no sum across units, every split the same bits;
+//   PL_PAYLOAD  delta and those partial sums alone (npc = 0, U = sx ngrp chain units): no panel of the powers, no P' block, no block or tail store.
 #pragma once
 
 #define PL_KS 32     // k-steps of 4 (n <= 128)
 #define PL_NT 512    // most threads per workgroup (8 row tiles)
 #define PL_NP 8      // B^{+-} value pairs per thread (the host keeps n npc / 2 <= PL_NP blockDim)
 #define PL_SLACK 128 // doubles behind the last column block: the B operand loads of a column run 128 rows whatever n is
+enum { PL_FULL = 0, PL_COMPACT = 1, PL_MERIT = 2, PL_PAYLOAD = 3 };
 
 // one 16 x 16 tile of G * B: a[] = this wave's rows of G, Bp = this lane's column of B in LDS + (lane >> 4), kmask = the k-steps with a nonzero
 // in the wave's rows (wave-uniform).  Operand loads are unconditional, base + immediate: every double of the workgroup's LDS is finite
@@ -45,8 +55,10 @@ __device__ __forceinline__ double4_t pl_tile(const double (&a)[PL_KS], const dou
 }
 
 // p.S = U units per interval, p.nc state columns per chain unit; sx state-column slices, mg drives per group, npc power columns per unit
-template <bool JAC>
+template <bool JAC, int MODE = PL_FULL>
 __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, const int sx, const int mg, const int npc) {
+    static_assert(JAC || MODE == PL_FULL, "the modes belong to the Jacobian launch");
+    constexpr bool PANEL = JAC && MODE != PL_PAYLOAD;  // the panel of the powers and of B^{+-}
     extern __shared__ double lds[];
     const int n = p.n, d = p.cols, m = p.m, LD = p.LD, nc = p.nc, q = p.q, U = p.S;
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, rt = tid >> 6;  // one wave per row tile
@@ -65,11 +77,11 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
     const int c0 = s * nc, nce = chain ? max(0, min(nc, d - c0)) : 0;           // this unit's state columns
     const int l0 = g * mg, mge = (JAC && chain) ? max(0, min(mg, m - l0)) : 0;  // ... and drives
     const int T = JAC ? 2 + mg : 1, LDc = LD * nc;
-    const int pc0 = JAC ? u * npc : n, npce = max(0, min(npc, n - pc0));        // ... and columns of the powers
+    const int pc0 = PANEL ? u * npc : n, npce = max(0, min(npc, n - pc0));      // ... and columns of the powers
     double *G = lds;
     double *Sm = G + LD * n, *Dm = Sm + LDc, *Xc = Dm + LDc, *Xn = Xc + T * LDc;  // X: W | V | dW_l0 .. (JAC), W alone otherwise
     double *Pn = Xn + T * LDc, *Pc = G + LD * (npce > 0 ? pc0 : 0);
-    double *us = Pn + (JAC ? LD * npc : 0) + PL_SLACK;
+    double *us = Pn + (PANEL ? LD * npc : 0) + PL_SLACK;
     for (int e = tid; e < p.lds_doubles; e += nth) lds[e] = 0.0;
     __syncthreads();
     const int x_off = p.x_offs[p.z_batch_stride ? 0 : b];
@@ -106,7 +118,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
     int o_[PL_NP];
     double hp = h, hm = -h;
     const int ptot = n * npce;
-    if (JAC) {
+    if (PANEL) {
 #pragma unroll
         for (int r = 0; r < PL_NP; ++r) {
             const int pos = 2 * (tid + nth * r);
@@ -125,7 +137,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
             }
         }
     }
-    const int cx = chain ? T * nc : 0, ct_n = (cx + (JAC ? npc : 0) + 15) >> 4;
+    const int cx = chain ? T * nc : 0, ct_n = (cx + (PANEL ? npc : 0) + 15) >> 4;
     const int ew = p.ell_w;
     for (int j = q - 1; j >= 0; --j) {
         const double *Yj = (j & 1) ? Sm : Dm;
@@ -177,7 +189,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
         double *t_ = Xc;
         Xc = Xn;
         Xn = t_;
-        if (JAC && j > 0) {  // the next power: its term of B^{+-}
+        if (PANEL && j > 0) {  // the next power: its term of B^{+-}
             t_ = Pc;
             Pc = Pn;
             Pn = t_;
@@ -199,10 +211,26 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
     if (p.delta && g == 0)
         for (int e = tid; e < nce * n; e += nth) p.delta[item * xd + (long long)c0 * n + e] = Xc[(e % n) + LD * (e / n)];
     if (!JAC) return;
-    double *jb = p.jac + item * p.jac_per;
-    const long long blk = (long long)d * nn;
-    // tails [c][l | dt][i]: this group's drives, and the dt block from group 0
     const int nl = mge + (g == 0 ? 1 : 0);
+    if (MODE == PL_MERIT || MODE == PL_PAYLOAD) {
+        // the payload's partial sums of this unit's columns: jobs t < mge its drives, then (group 0) dt and <lam, delta>; lam = delta is read from W in LDS
+        const int nj = nl + (g == 0 ? 1 : 0), nw = nth >> 6;
+        const double *lamg = p.mlam ? p.mlam + item * xd + (long long)c0 * n : nullptr;
+        for (int job = rt; job < nce * nj; job += nw) {
+            const int c = job / nj, t = job - c * nj;
+            const double *x = Xc + (t < mge ? 2 + t : (t == mge ? 1 : 0)) * LDc + LD * c;
+            double sacc = 0.0;
+            for (int i = lane; i < n; i += 64) sacc = __builtin_fma(x[i], lamg ? lamg[c * n + i] : Xc[i + LD * c], sacc);
+            for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
+            if (t == mge + 1 && !lamg) sacc *= 0.5;
+            if (lane == 0) p.mpart[(item * d + c0 + c) * (m + 2) + (t < mge ? l0 + t : m + (t - mge))] = sacc;
+        }
+        if (MODE == PL_PAYLOAD) return;
+    }
+    double *jb = p.jac + item * p.jac_per;
+    const int dcp = MODE == PL_COMPACT ? 1 : d;  // copies of a block in the layout
+    const long long blk = (long long)dcp * nn;
+    // tails [c][l | dt][i]: this group's drives, and the dt block from group 0
     double *jt = jb + 2 * blk;
     for (int e = tid; e < nl * nce * n; e += nth) {
         const int i = e % n, t = (e / n) % nl, c = e / (n * nl);
@@ -216,7 +244,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
         if (o_[r] >= 0) {
             const int pos = 2 * (tid + nth * r);
             double *o0 = jb + (long long)pc0 * n + pos;
-            for (int c = 0; c < d; ++c) {
+            for (int c = 0; c < dcp; ++c) {
                 if (even) {
                     store2(o0 + c * nn, -bp[r][0], -bp[r][1], p.nt);
                     store2(o0 + blk + c * nn, bm[r][0], bm[r][1], p.nt);

@@ -51,6 +51,53 @@ __global__ __launch_bounds__(256) void pcl_expand_kernel(const double *__restric
     }
 }
 
+// The same for a large context (PCL_LARGE_N, option large_reduce): a tile has up to 8192 element pairs (n = 128), so a (sign, slice) is split
+// over P = ceil(n^2 / 4096) workgroups of 2048 pairs each -- 2 at n = 66 .. 90, 3 up to 110, 4 up to 128; the rule stays: request everything, then
+// only issue the 16-byte stores of the slice's copies.  n is even wherever blocks are replicated (cols > 1: n = 2 d).  Tail workgroups as above.
+//   per interval: 2 S P block workgroups in address order (sign, slice, part), then T tail workgroups.  Copies only: the bits of the compact values.
+__device__ __host__ __forceinline__ int pcl_expand_large_parts(int n) { return (int)((((long long)n * n >> 1) + 2047) / 2048); }
+__global__ __launch_bounds__(256) void pcl_expand_large_kernel(const double *__restrict__ compact, double *__restrict__ full,
+                                                               int d, int n, int m, long long n_bk, int cpi, int nt) {
+    const long long nn = (long long)n * n, xd = (long long)n * d;
+    const long long cper = 2 * nn + xd * (m + 1), fper = 2 * d * nn + xd * (m + 1);
+    const int S = (d + cpi - 1) / cpi, P = pcl_expand_large_parts(n);
+    const long long tail2 = (xd * (m + 1)) >> 1;  // element pairs of the tail run
+    const int T = (int)((tail2 + 2047) / 2048);
+    const int per_bk = 2 * S * P + T;
+    const long long bk = blockIdx.x / per_bk;
+    const int r = (int)(blockIdx.x - bk * per_bk);
+    if (bk >= n_bk) return;
+    const double *src = compact + bk * cper;
+    double *dst = full + bk * fper;
+    const int tid = threadIdx.x;
+    double2_t v[8];
+    if (r < 2 * S * P) {
+        const int sign = r / (S * P), sl = (r - sign * S * P) / P, part = r - (sign * S + sl) * P;
+        const int c0 = sl * cpi, c1 = min(d, c0 + cpi);
+        const int nn2 = (int)(nn >> 1), e0 = part * 2048;  // this workgroup's pairs [e0, e0 + 2048) of the tile
+        src += sign * nn;
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (e0 + tid + 256 * q < nn2) v[q] = *reinterpret_cast<const double2_t *>(src + 2 * (e0 + tid + 256 * q));
+        double *o = dst + ((long long)sign * d + c0) * nn;
+        for (int c = c0; c < c1; ++c, o += nn) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (e0 + tid + 256 * q < nn2) store2(o + 2 * (e0 + tid + 256 * q), v[q][0], v[q][1], nt);
+        }
+    } else {
+        const long long e0 = (long long)(r - 2 * S * P) * 2048;
+        src += 2 * nn;
+        dst += 2 * d * nn;
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (e0 + tid + 256 * q < tail2) v[q] = *reinterpret_cast<const double2_t *>(src + 2 * (e0 + tid + 256 * q));
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (e0 + tid + 256 * q < tail2) store2(dst + 2 * (e0 + tid + 256 * q), v[q][0], v[q][1], nt);
+    }
+}
+
 // The same for a context of the exponential constraint (option exp_full): compact [-E (n n) | tail] -> full [-E x cols | ones (x_dim) | tail].
 //   per interval: S block workgroups (a slice of cpi state columns each: the tile is read once, then only stores) and T tail workgroups
 //   (4096 doubles each; the first also writes the ones).  16-byte accesses where n is even and both arrays are 16-byte aligned (every

@@ -74,10 +74,11 @@ struct pcl_ctx {
     int n, K;
     int cols;  // state columns (d for unitaries, 1 for kets)
     int vec = 0;  // PCL_STATE_VECTOR: n = desc.d (general generator on one column; general-order kernel only)
-    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every residual / Jacobian launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); compact Jacobian and merit / reduce are refused, and so are the Hessian of the Lagrangian, the rollout and the objective without the options below
+    int large = 0;  // PCL_LARGE_N with 66 <= n <= 128: every residual / Jacobian launch is pcl_pade_large_kernel (pcl_kernel_pade_large.hpp); compact Jacobian and merit / reduce are refused without the option large_reduce, and so are the Hessian of the Lagrangian, the rollout and the objective without the options below
     int large_hess = 0;                    // ... option large_hess: the Hessian of the Lagrangian is served (pcl_kernel_pade_large_hess.hpp)
     int64_t opt_large_hess_drives = 0;     // ... ... the most drives per group of that launch (0 auto: as many as fit)
     int large_full = 0;                    // ... option large_full: the objective family and the rollout are served (pcl_kernel_large_rollout.hpp; its workspace is dexpm)
+    int large_reduce = 0;                  // ... option large_reduce: the compact Jacobian trio, the host calls' compact route and the merit / reduce payload are served (the modes of pcl_kernel_pade_large.hpp, pcl_expand_large_kernel)
     int64_t opt_large_rollout_stage = 0;   // ... ... measurements: 0 both launches of the rollout | 1 the propagators only | 2 the chain only, on the workspace as it stands
     double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
@@ -409,6 +410,12 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 #define LARGE_FULL_GATE(ctx, what)                                \
     do {                                                          \
         if ((ctx) && !(ctx)->large_full) LARGE_NOTIMPL(ctx, what); \
+    } while (0)
+
+// ... and the compact Jacobian trio and the merit / reduce entry points by option large_reduce only: without it, the same words
+#define LARGE_REDUCE_GATE(ctx, what)                                \
+    do {                                                            \
+        if ((ctx) && !(ctx)->large_reduce) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
 #define EXP_HESS_GATE(ctx, what)                       \
@@ -803,7 +810,7 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 }
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    LARGE_NOTIMPL(ctx, "pcl_jac_compact_nnz");
+    LARGE_REDUCE_GATE(ctx, "pcl_jac_compact_nnz");
     VAR_COMPACT_GATE(ctx, "pcl_jac_compact_nnz");
     EXP_FULL_GATE(ctx, "pcl_jac_compact_nnz");
     if (per) *per = jac_per_compact(ctx);
@@ -1183,14 +1190,14 @@ extern "C" int pcl_jac_dev(pcl_ctx *ctx, const double *Z, double *vals) {  // ev
 extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *delta, double *compact) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !compact) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_compact_dev: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_eval_jac_compact_dev");
+    LARGE_REDUCE_GATE(ctx, "pcl_eval_jac_compact_dev");
     EXP_FULL_GATE(ctx, "pcl_eval_jac_compact_dev");
     return launch_fused(ctx, Z, delta, compact, true);
 }
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
-    LARGE_NOTIMPL(ctx, "pcl_jac_expand_dev");
+    LARGE_REDUCE_GATE(ctx, "pcl_jac_expand_dev");
     VAR_COMPACT_GATE(ctx, "pcl_jac_expand_dev");
     EXP_FULL_GATE(ctx, "pcl_jac_expand_dev");
     ON_DEVICE(ctx);
@@ -1221,6 +1228,15 @@ extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *v
     // slices of 3 state columns (70 KB per workgroup at config 3), the option cols_per_slice overrides
     const int cpi = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_cols_per_slice > 0 ? ctx->opt_cols_per_slice : 3, ctx->cols));
     const long long tail2 = ((long long)ctx->x_dim * (ctx->desc.n_drives + 1)) >> 1;
+    if (ctx->large) {  // tiles of up to 8192 element pairs (option large_reduce): workgroups of 2048 pairs each per (sign, slice) -- pcl_expand_large_kernel
+        const long long per_bk_l = 2LL * pcl_expand_large_parts(ctx->n) * ((ctx->cols + cpi - 1) / cpi) + (tail2 + 2047) / 2048;
+        const long long grid_l = n_bk * per_bk_l;
+        if (grid_l > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid_l);
+        hipLaunchKernelGGL(pcl_expand_large_kernel, dim3((unsigned)grid_l), dim3(256), 0, ctx->stream, compact, vals, ctx->cols, ctx->n, ctx->desc.n_drives, n_bk, cpi,
+                           (int)(ctx->opt_nt > 0 ? ctx->opt_nt : 0));
+        HIP_TRY(ctx, hipGetLastError());
+        return PCL_OK;
+    }
     const long long per_bk = 2LL * ((ctx->cols + cpi - 1) / cpi) + (tail2 + 2047) / 2048;
     const long long grid = n_bk * per_bk;
     if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid);
@@ -1388,7 +1404,8 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
     // (variational contexts without the option var_compact, and exponential ones without the option exp_full: full values, host_path 1)
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && !ctx->large && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
+    // (large contexts: by the option large_reduce)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->large || ctx->large_reduce) && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));

@@ -105,14 +105,29 @@ def _check_large_full(large_full, large_generator, pade_order, batch_mode=PCL_BA
         raise ValueError("large_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
 
 
+def _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_reduce`` (the library's option of that name: the compact Jacobian, the host-pointer calls' compact route and the merit /
+    reduce payload at generator dimensions 66 .. 128) goes with ``large_generator=True`` on the Pade constraint of a plain context: anything else is
+    a ``ValueError``, before any device call."""
+    if not large_reduce:
+        return
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("large_reduce=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)")
+    if not large_generator:
+        raise ValueError("large_reduce=True is the compact Jacobian and the reduce payload of a context created with large_generator=True: it needs that keyword")
+    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP:
+        raise ValueError("large_reduce=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
-                 large_generator=False, large_hessian=False, large_full=False):  # fmt: skip
+                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False):  # fmt: skip
         _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
         _check_large_full(large_full, large_generator, pade_order, batch_mode)
+        _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order, batch_mode)
@@ -168,6 +183,7 @@ class _PclContext:
         self.large = bool(large_generator) and n > 64
         self.large_hessian = False
         self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
+        self.large_reduce = False  # (``large_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
         if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
             self.set_option("var_exp_hess_tiles", 1)
         if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
@@ -183,6 +199,8 @@ class _PclContext:
             self.set_option("exp_full", 1)
         if large_full and self.large:  # (at n <= 64 the ordinary context serves objective and rollout as always: the option is not set)
             self.set_option("large_full", 1)
+        if large_reduce and self.large:  # (at n <= 64 the ordinary context serves them as always: the option is not set)
+            self.set_option("large_reduce", 1)
         if var_compact:
             self.set_option("var_compact", 1)
         # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
@@ -337,10 +355,13 @@ class _PclContext:
         if self.exp_hessian:
             self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz = a.value
-        if self.large:  # (no compact Jacobian; the Hessian of the Lagrangian by ``large_hessian`` only)
+        if self.large:  # (the compact Jacobian by ``large_reduce`` only; the Hessian of the Lagrangian by ``large_hessian`` only)
             if self.large_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
                 self.hess_nnz = a.value
+            if self.large_reduce:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+                self.compact_nnz = a.value
             return
         if self.exponential:  # (the compact Jacobian by ``exp_full`` only, the Hessian of the Lagrangian by ``exp_hessian`` only)
             if self.exp_full:
@@ -461,7 +482,8 @@ class _PclContext:
     def eval_jac_merit_dev(self, Z, lam, delta, vals, out):
         """``eval_jac_dev`` + ``merit_grad_dev`` in one pass over the state columns (pcl_eval_jac_merit_dev): the fused kernel
         forms the payload's dot products while a column's vectors are in LDS; same outputs as the two calls.  ``vals=None`` (an exponential
-        context with ``exp_full`` only): the residual and the payload without the Jacobian, one adjoint chain per interval."""
+        context with ``exp_full``: the residual and the payload without the Jacobian, one adjoint chain per interval; a large context with
+        ``large_reduce``: chain units only, no Jacobian value formed or written)."""
         self._chk(self._L.pcl_eval_jac_merit_dev(self._h, _ptr(Z), _ptr(lam), _ptr(delta), _ptr(vals), _ptr(out)))
 
     def eval_jac_merit_objective_dev(self, Z, lam, delta, vals, out, Q, value, grad):
@@ -516,6 +538,12 @@ class _PclContext:
             self.hess_nnz, self.hess_per = a.value, b.value
         if self.large and key == "large_full":
             self.large_full = bool(value)
+        if self.large and key == "large_reduce":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
+            self.large_reduce = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.large_reduce:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.compact_nnz, self.compact_per = a.value, b.value
         if key == "var_compact" and self.batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):  # ... the stacked state's compact Jacobian
             self.var_compact = bool(value)
             a, b = ctypes.c_int64(), ctypes.c_int64()
@@ -584,7 +612,7 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False):
+                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -606,9 +634,14 @@ class HipPadeIntegrator:
         64 the ordinary context serves its Hessian as always.
         ``large_full=True`` (the same conditions, else ``ValueError``): the objective family -- goals, weights, regularisers, value, gradient and the
         objective's Hessian -- and the rollout are served at those dimensions too (the library's option ``large_full``): ``rollout``, ``rollout_dev``
-        and ``Objective.bind`` work unchanged.  Independent of ``large_hessian``; at a dimension up to 64 the ordinary context serves them as always."""
+        and ``Objective.bind`` work unchanged.  Independent of ``large_hessian``; at a dimension up to 64 the ordinary context serves them as always.
+        ``large_reduce=True`` (the same conditions, else ``ValueError``): the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``, ``eval_jac_compact_dev``,
+        ``jac_expand_dev``), the host-pointer calls' compact route and the merit / reduce payload (``merit_grad_dev``, ``eval_jac_merit_dev`` -- with
+        ``vals=None`` the payload alone -- and, together with ``large_full``, ``eval_jac_merit_objective_dev``) are served at those dimensions too (the
+        library's option ``large_reduce``).  Independent of the other two; at a dimension up to 64 the ordinary context serves them as always."""
         _check_large_hessian(large_hessian, large_generator, pade_order)
         _check_large_full(large_full, large_generator, pade_order)
+        _check_large_reduce(large_reduce, large_generator, pade_order)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order)
         _check_var_compact(var_compact)
@@ -652,7 +685,7 @@ class HipPadeIntegrator:
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
             state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
-            large_hessian=large_hessian, large_full=large_full,
+            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
         )  # fmt: skip
         self._large_generator = bool(large_generator)
         if pade_order == 0:
@@ -716,9 +749,10 @@ class HipVariationalIntegrator:
     path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False, large_full=False):
+                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False):
         _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
+        _check_large_reduce(large_reduce, False, pade_order, PCL_BATCH_VARIATIONAL)
         exp_hessian = _exp_hessian_value(exp_hessian)
         if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
             raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))

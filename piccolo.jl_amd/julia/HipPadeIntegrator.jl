@@ -86,7 +86,13 @@ end
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
                       exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
-                      large_hessian::Bool = false, large_full::Bool = false)
+                      large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false)
+    # large_reduce = true (the same conditions): the library's option large_reduce -- pcl_jac_compact_nnz, pcl_eval_jac_compact_dev, pcl_jac_expand_dev,
+    # the host-pointer calls' compact route and the merit / reduce entry points are served at those dimensions too.  Independent of the other two.
+    (large_reduce && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_reduce = true is the compact Jacobian and the reduce payload of a context created with large_generator = true: it needs that keyword"))
+    (large_reduce && pade_order == PCL_ORDER_EXP) &&
+        throw(ArgumentError("HipPadeIntegrator: large_reduce = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large contexts"))
     # large_full = true (the same conditions): the library's option large_full -- goals, weights, regularisers, pcl_objective*, pcl_objective_hess*
     # and pcl_rollout* are served at those dimensions too.  Independent of large_hessian; at n <= 64 the ordinary context serves them as always.
     (large_full && !large_generator) &&
@@ -132,6 +138,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
     (large && large_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_hess", 1))
     (large && large_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_full", 1))
+    (large && large_reduce) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_reduce", 1))
     ((pade_order == PCL_ORDER_EXP && !exp_hessian) || (large && !large_hessian)) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
@@ -200,7 +207,7 @@ end
 # the compact path (one -E per interval over PCIe, replicated by the host's threads) with the bits of the full path, and the compact /
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
-const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true
+const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -300,7 +307,8 @@ end
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false)
+                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false)
+    large_reduce && throw(ArgumentError("HipPadeIntegrator: large_reduce = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)"))
     large_full && throw(ArgumentError("HipPadeIntegrator: large_full = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)"))
     large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
     pade_order = _order_code(pade_order)
