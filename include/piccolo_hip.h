@@ -522,7 +522,8 @@ int pcl_codegen_source_v4(int d, int m, const double *G0, int n_g0, const double
  * libhiprtc, no device.  what: 0 fused residual + Jacobian (+ residual only) at order 2q | 1 general-order Hessian, one workgroup per
  * interval | 2 ... two workgroups per interval | 3 the order-4 Hessian / value-table module (q ignored) | 4 the fused module with the
  * slice-ticket roles (launches of several trajectories) | 5 general-order Hessian, one wave per group of state columns (`auto` at every
- * order but 4).  (6, the resident evaluator's module, in lab builds only: piccolo_hip_lab.h.) */
+ * order but 4) | 7 the fused module of the launches with one item per workgroup (one trajectory per launch; option v4_one_item).  (6, the
+ * resident evaluator's module, in lab builds only: piccolo_hip_lab.h.) */
 int pcl_jit_prebuild(int d, int m, const double *G0, int n_g0, const double *Gj, int q, int what, const char *out_dir);
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Registers, spills, LDS and text size of the pattern-compiled modules of a BASELINE config as the library compiles them (no GPU needed):
-module_stats.py [config=3] [order=4] [what=0 ...]   (what: pcl_jit_prebuild's; 0 fused lean, 4 fused with ticket roles, 1/2/3 Hessian)"""
+module_stats.py [config=3] [order=4] [what=0 ...]   (what: pcl_jit_prebuild's; 0 fused lean, 4 fused with ticket roles, 7 fused with one item per workgroup, 1/2/3 Hessian)"""
 import os, subprocess, sys, tempfile, glob
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import ctypes
@@ -35,3 +35,6 @@ for what in whats:
                 open(os.environ["KEEP"], "wb").write(blob[24 + n:])  # the code object, for llvm-objdump -d
             print("what %d:" % what, "; ".join(keep))
             print("   ", text[0].split()[-6:] if text else "")
+            syms = subprocess.run([readelf, "-s", "-W", co], capture_output=True, text=True).stdout  # text per kernel (the section holds every kernel of the module)
+            for name, size in sorted({(w[7], int(w[2], 0)) for w in (l.split() for l in syms.splitlines()) if len(w) >= 8 and w[3] == "FUNC"}):
+                print("    %s: %d B of text" % (name, size))

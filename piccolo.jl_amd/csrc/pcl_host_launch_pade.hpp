@@ -467,6 +467,29 @@ static int launch_fused_v4(pcl_ctx *ctx, KParams &p, bool compact, bool want_mer
         else
             return launch_fused_v4_static(ctx, p, compact, want_merit);
     }
+    // ONE item per workgroup (one trajectory per launch, or a few: as many workgroups as round-robin slices): a module of its own, the same kernel
+    // text with this launch's shape folded in as constants (SP4_ONE_ITEM) -- the general module carries item loops, three work splits, four tail
+    // modes, the A/B flags and the reduce payload through a launch whose start-up counts.  Same arithmetic, same bits.
+    bool one_item = !ticket && !compact && !p.contig && units == g && ctx->opt_grid <= 0 && !want_merit && !p.mpart && p.tail_mode == 3 && p.v4_flags == 0 && !ctx->res_capture;
+#ifdef PCL_PROFILE
+    if (p.prof & (2 | 4 | 8 | 32 | 256)) one_item = false;  // (the experiments live in the general module; the stamps are in both)
+#endif
+    if (ctx->opt_v4_one_item == 1 && !one_item)
+        return fail(ctx, PCL_ESHAPE, "v4_one_item=1: the one-item module serves full-value launches of one round-robin slice per workgroup (no tickets, no contiguous ranges, no grid option, no reduce payload, v4_tail_mode 3, v4_flags 0)");
+    one_item = one_item && ctx->opt_v4_one_item != 0 && !ctx->v4_f1_failed;
+    if (one_item && !ctx->v4_f1) {  // compiled on the first such launch
+        const std::string src = v4_source(*ctx->v4_plan, p.q, np, (int)ctx->opt_v4_variant, 3);
+        const std::string key = "fused-sparse-one-item:" + std::to_string(p.q) + ":" + std::to_string(std::hash<std::string>{}(src));
+        ctx->v4_f1 = jit_compile(ctx->device, key, src, "pcl_fused_sparse_kernel", true);
+        if (!ctx->v4_f1) {
+            ctx->v4_f1_failed = 1;
+            // the general module computes the same bits: noted once, an error only under require_jit
+            if (jit_fell_back(ctx, "residual + Jacobian (one item per workgroup; the general module runs instead)") == PCL_EHIP) return PCL_EHIP;
+            one_item = false;
+        }
+    }
+    if (one_item) fk = ctx->v4_f1;
+    ctx->last_v4_one_item = one_item ? 1 : 0;
 #ifdef PCL_LAB
     if (ctx->res_capture) {  // pcl_resident_start: the launch as data
         ctx->res.p = p, ctx->res.tab = T.tab, ctx->res.dcf = T.dcf, ctx->res.grid = g, ctx->res.lds = lds, ctx->res.block = 64u * (unsigned)(m + 9);

@@ -77,7 +77,7 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         ctx->opt_prof = v;
     else if (!strcmp(key, "v4_variant")) {  // timing variants of kernel 4's generated product (WRONG results); recompiles
         ctx->opt_v4_variant = v;
-        ctx->v4_f = ctx->v4_ft = ctx->v4_feval = ctx->v4_fevalc = ctx->v4_fhess = ctx->v4_fhess2 = ctx->v4_fhessc = nullptr;
+        ctx->v4_f = ctx->v4_ft = ctx->v4_f1 = ctx->v4_feval = ctx->v4_fevalc = ctx->v4_fhess = ctx->v4_fhess2 = ctx->v4_fhessc = nullptr;
     }
 #endif
     else if (!strcmp(key, "host_threads"))  // host-pointer entry points: threads expanding the compact values (0 = auto)
@@ -117,6 +117,8 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         ctx->opt_v4_flags = v;
     else if (!strcmp(key, "v4_ticket"))  // kernel 4: work items by ticket (-1 auto: full-value launches of several intervals per CU | 0 static split | 1)
         ctx->opt_v4_ticket = v < 0 ? -1 : (v != 0);
+    else if (!strcmp(key, "v4_one_item"))  // kernel 4: the module of launches with one item per workgroup (-1 auto: wherever it serves | 0 the general module | 1 require: a launch it does not serve is an error)
+        ctx->opt_v4_one_item = v < 0 ? -1 : (v != 0);
     else if (!strcmp(key, "v4_ticket_cols"))  // ... state columns per slice ticket (0 auto: 4 since round 5; 3 in round 4)
         ctx->opt_v4_ticket_cols = v < 0 ? 0 : v;
     else if (!strcmp(key, "v4_ticket_ahead"))  // ... slices taken ahead of the one being stored (0 | 1)
@@ -313,6 +315,10 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->opt_v4_ticket_ahead;
     else if (!strcmp(key, "last_v4_ticket"))
         *v = ctx->last_v4_ticket;
+    else if (!strcmp(key, "v4_one_item"))
+        *v = ctx->opt_v4_one_item;
+    else if (!strcmp(key, "last_v4_one_item"))
+        *v = ctx->last_v4_one_item;
     else if (!strcmp(key, "hess_kernel"))
         *v = ctx->opt_hess_kernel;
     else if (!strcmp(key, "eval_kernel"))

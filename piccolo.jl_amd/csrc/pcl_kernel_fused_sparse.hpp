@@ -101,6 +101,33 @@ static __device__ __forceinline__ unsigned sp4_lds_off(const double *q) {
 #ifndef SP4_RESIDENT
 #define SP4_RESIDENT 0            // 1: the module of the RESIDENT evaluator (pcl_resident_*): the evaluation below as a device function, called once per posted request
 #endif
+// The launch's shape as the kernel reads it.  SP4_ONE_ITEM 1: the module of the launches in which EVERY workgroup has exactly one item (as many
+// workgroups as round-robin slices: one trajectory per launch, or a few) -- the static split without contiguous ranges, full values, no reduce
+// payload, tails by the stream waves, no A/B flags, no profiling experiments beyond the stamps (the host checks all of it: launch_fused_v4).  What
+// the general module reads from KParams is a constant here: the item loops of every role run once and fold away, the P wave's loop is dead behind
+// the cooperative start, nothing of the work split's arithmetic stands ahead of the start barrier.  Same expressions, same arithmetic, same bits.
+#ifndef SP4_ONE_ITEM
+#define SP4_ONE_ITEM 0
+#endif
+#if SP4_ONE_ITEM
+#if SP4_TICKETS || SP4_RESIDENT
+#error "SP4_ONE_ITEM is a flavour of the static-split kernel module"
+#endif
+#define SP4_CONTIG false
+#define SP4_COMPACT false
+#define SP4_FLAGS 0
+#define SP4_TAIL_MODE 3
+#define SP4_MPART ((double *)nullptr)
+#define SP4_PROF (p.prof & ~(2 | 4 | 8 | 32 | 256))  // (the stamps stay)
+#else
+#define SP4_CONTIG p.contig
+#define SP4_COMPACT p.compact
+#define SP4_FLAGS p.v4_flags
+#define SP4_TAIL_MODE p.tail_mode
+#define SP4_MPART p.mpart
+#define SP4_PROF p.prof
+#endif
+
 #if SP4_RESIDENT
 extern "C" {  // (the dynamic LDS array is declared by extern "C" kernels too: one language linkage)
 static __device__ __forceinline__ void sp4_fused_body(const KParams &p, const double *__restrict__ drift_tab, const double *__restrict__ mags_, const double *__restrict__ dcf_tab) {
@@ -125,7 +152,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
     do {                                                                                                                     \
         if (p.dbg && blockIdx.x == 0 && lane == 0 && stamp_ < 32) p.dbg[32 * wave + stamp_++] = (long long)__builtin_amdgcn_s_memtime(); \
     } while (0)
-    const bool no_blocks = p.prof & 2, no_chains = p.prof & 4, no_tails = p.prof & 8;
+    const bool no_blocks = SP4_PROF & 2, no_chains = SP4_PROF & 4, no_tails = SP4_PROF & 8;
 #else
 #define SP4_STAMP() do { } while (0)
     constexpr bool no_blocks = false, no_chains = false, no_tails = false;
@@ -137,12 +164,16 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
     if (wall_ && tid == 0) wall_[0] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
     // ---- work split (as kernel 3) ----------------------------------------------------------------------------------------
-    const long long blk = p.compact ? (long long)nn : (long long)d * nn;  // size of the -B^+ / of the B^- segment
+    const long long blk = SP4_COMPACT ? (long long)nn : (long long)d * nn;  // size of the -B^+ / of the B^- segment
     const long long xd = (long long)n * d;
     const int bx = (int)blockIdx.x;
+#if SP4_ONE_ITEM
+    constexpr int n_my = 1;  // (the grid is the number of items)
+    constexpr long long g_lo = 0, g_hi = 0;
+#else
     int n_my;
     long long g_lo = 0, g_hi = 0;
-    if (p.contig) {
+    if (SP4_CONTIG) {
         const long long tot = (long long)p.batch * p.K * d;
         g_lo = tot * bx / (long long)gridDim.x;
         g_hi = tot * (bx + 1) / (long long)gridDim.x;
@@ -151,8 +182,9 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
         const int n_items = p.batch * p.K * p.S;
         n_my = n_items > bx ? (n_items - bx + (int)gridDim.x - 1) / (int)gridDim.x : 0;
     }
+#endif
     auto decode = [&](int it, int &c0, int &nce, int &k, int &b) {
-        if (p.contig) {
+        if (SP4_CONTIG) {
             const long long bk = g_lo / d + it;
             c0 = it == 0 ? (int)(g_lo - bk * d) : 0;
             nce = (int)min((long long)d, g_hi - bk * d) - c0;
@@ -220,7 +252,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
     };
     // Counters zero.  The tiles start as whatever the previous workgroup left: every entry a wave reads has been written by the item
     // that reads it (zeroing 150 KB took 0.84 us of a 24 us workgroup life).  v4_flags & 8 (tests): NaN everywhere first.
-    if (p.v4_flags & 8)
+    if (SP4_FLAGS & 8)
         for (int e = tid; e < SP4_NTILES * SP4TILE; e += 64 * SP4_NWAVES) lds[e] = __builtin_nan("");
 #ifdef PCL_PROFILE
     if (p.prof & 128) SP4_STAMP();
@@ -256,10 +288,10 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
             store2(dst + 2 * e2, src[0], src[1], nt);
         }
     };
-    const bool tails_by_stream = p.tail_mode == 3 && !tick;  // (ticket mode: the writer wave -- the item whose tails are ready is not the stream's)
+    const bool tails_by_stream = SP4_TAIL_MODE == 3 && !tick;  // (ticket mode: the writer wave -- the item whose tails are ready is not the stream's)
     // the chains may rewrite their tiles once item it - 1 has left them
     auto outputs_taken = [&](int it) {
-        if (!tails_by_stream || p.mpart) gave_up = sp4_wait(sync, SP4_F_OC, it, gave_up);
+        if (!tails_by_stream || SP4_MPART) gave_up = sp4_wait(sync, SP4_F_OC, it, gave_up);
         if (tails_by_stream) {
             for (int w = 0; w < SP4_NSTREAM; ++w) gave_up = sp4_wait(sync, SP4_F_TS + w, it, gave_up);
         }
@@ -285,19 +317,19 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
     // each (sp4_product0_part: nobody can store before the powers exist; a lone P wave takes 7.7 k cycles for G, G^2 at order 4 -- a
     // fifth of a one-trajectory launch).  Needs fully resident coefficients (the generator then emits the parts).  The P wave's own loop
     // starts with item 1.
-    const bool coop = SP4_COOP && !(p.v4_flags & 4) && !tick;
+    const bool coop = SP4_COOP && !(SP4_FLAGS & 4) && !tick;
     // ... with ALL q powers resident even where the ring is shorter (orders 8 and 10 at config 3: three power tiles): the chains of the first
     // item start behind the stream's folds anyway (chains_may_start), so until then their dW tiles are free -- powers npw + 1 .. q of the FIRST
     // item live there.  No product waits for a fold, no fold for a tile (order 10 ran without the cooperative start before: five powers
     // through three tiles were slower than a lone P wave).  Needs q - npw <= m and the chains held back (v4_flags & 16 off).
-    const bool borrow = coop && q > npw && q - npw <= m && !(p.v4_flags & 16);
+    const bool borrow = coop && q > npw && q - npw <= m && !(SP4_FLAGS & 16);
     // ONE-item workgroups (one trajectory per launch) at orders 8 and 10 are bound by the CHAINS, not by the stores: W's level s + 1 overwrites
     // the tile the m drive waves gather level s from, so W and the dW_l advance in lock step -- q x (W product + gather + dW product), 44 k cycles
     // at order 8 against 33 k of block stores (stamps, round 5).  With nothing behind the first item the power tiles are free once the stream has
     // folded them: W alternates between its tile and power tile 0 and runs a level ahead of the gathers; the dW chains no longer wait for it.
     // (measured, one trajectory per launch, with / without: order 10 29.5 / 32.0 us, order 8 27.7 / 28.1, order 6 26.2 / 25.7, order 4 equal: from order 8 on;
     //  v4_flags & 64 switches it off)
-    const bool pingpong = coop && n_my == 1 && !(p.v4_flags & (16 | 64)) && q >= 4;
+    const bool pingpong = coop && n_my == 1 && !(SP4_FLAGS & (16 | 64)) && q >= 4;
     double *const Walt = pingpong ? Pt : Wt;                   // W after an odd number of steps
     const double *const Wfin = (pingpong && (q & 1)) ? Pt : Wt;  // delta = W after q steps
     Wres = Wfin;
@@ -307,7 +339,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
     // ... and the chains of that item start behind them: twelve waves of products on four SIMDs ran the stream's parts three times
     // slower (4.1 k cycles instead of 1.3 k), and the chains have the whole store phase to finish in
     auto chains_may_start = [&](int it) {
-        if (coop && it == 0 && !(p.v4_flags & 16))
+        if (coop && it == 0 && !(SP4_FLAGS & 16))
             for (int w = 0; w < SP4_NSTREAM; ++w) gave_up = sp4_wait(sync, SP4_F_C + w, q, gave_up);
     };
 
@@ -404,7 +436,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
         SP4_SCALARS_DEF();
         if (wave == 0) {
             // ---- P: powers of G(u_k), one tile of the ring per power -----------------------------------------------------------
-            if (!(p.v4_flags & 1)) __builtin_amdgcn_s_setprio(2);  // the stream waits for this chain
+            if (!(SP4_FLAGS & 1)) __builtin_amdgcn_s_setprio(2);  // the stream waits for this chain
             // slice tickets: the builds follow the group's static visit order, jumping to the visit the dispatcher is at when that is ahead (the
             // intervals in between were exhausted before this workgroup got there); the controls and the step come from the dispatcher's ring
             int pv = -1;
@@ -473,7 +505,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
                     }
 #ifdef PCL_PROFILE
                     SP4_STAMP();
-                    const int reps = (p.prof & 32) ? 17 : 1;  // the product's warm rate: sixteen more of it (same result)
+                    const int reps = (SP4_PROF & 32) ? 17 : 1;  // the product's warm rate: sixteen more of it (same result)
                     for (int rep = 0; rep < reps; ++rep) {
                         if (act) sp4_product0(x, 0u, sp4_lds_off(Po + own), sp4_lds_off(Po + oth), 0.0, 1.0, bs, tab, cf);
                         if (rep == 0) SP4_STAMP();
@@ -618,7 +650,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
                 nce = d;
                 // the chains follow the block front (a few visits ahead of it) instead of racing through the launch: their loads, products and
                 // tail stores are spread over the launch, and an interval's tails are written when its blocks are
-                if (!(p.v4_flags & 64)) gave_up = sp4_wait(sync, SP4_F_V, (iv - grp) / n_groups - 8, gave_up);
+                if (!(SP4_FLAGS & 64)) gave_up = sp4_wait(sync, SP4_F_V, (iv - grp) / n_groups - 8, gave_up);
             } else if (!chain_item(it, c0, nce, k, b))
                 break;
             SP4_STAMP();
@@ -662,13 +694,13 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
         // (pcl_eval_jac_merit_dev): per state column <d delta/d u_l, lam>, <d delta/d h, lam>, <delta, lam> (lam = delta: half the
         // squared norm) while the vectors are still in their tiles -- the tails are never read back from memory.  Lane (half, c) adds
         // its half of column c in row order, then the two halves: bitwise repeatable and independent of the work split.
-        for (int it = 0; !no_chains && (!tails_by_stream || p.mpart); ++it) {
+        for (int it = 0; !no_chains && (!tails_by_stream || SP4_MPART); ++it) {
             int c0, nce, k, b;
             if (!chain_item(it, c0, nce, k, b)) break;
             const long long bk = (long long)b * p.K + k;
             for (int w = 0; w < SP4_NOUT; ++w) gave_up = sp4_wait(sync, SP4_F_O + w, it + 1, gave_up);
             SP4_STAMP();
-            if (p.mpart) {
+            if (SP4_MPART) {
                 SP4_LANEPOS();
                 const bool act = c < nce;
                 double lam[SPD];
@@ -693,10 +725,10 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
                     }
                     double acc = a0 + a1;
                     acc += __shfl_xor(acc, 32, 64);
-                    if (act && half == 0) p.mpart[(bk * d + c0 + c) * (m + 2) + l] = (l == m + 1 && !p.mlam) ? 0.5 * acc : acc;
+                    if (act && half == 0) SP4_MPART[(bk * d + c0 + c) * (m + 2) + l] = (l == m + 1 && !p.mlam) ? 0.5 * acc : acc;
                 }
             }
-            if (!tails_by_stream && !no_tails) store_outputs(c0, nce, bk, 0, 1, p.tail_mode);
+            if (!tails_by_stream && !no_tails) store_outputs(c0, nce, bk, 0, 1, SP4_TAIL_MODE);
             wave_lds_sync();
             sp4_post(sync + SP4_F_OC, it + 1, lane);  // the chains may rewrite their tiles
             SP4_STAMP();
@@ -769,7 +801,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
         constexpr int pstep = (64 * SP4_NSTREAM) / hn > 0 ? (64 * SP4_NSTREAM) / hn : 1;
         constexpr int NSP = (n + pstep - 1) / pstep;  // column positions per thread
 #ifdef PCL_PROFILE
-        bool dry_ = (p.prof & 256) != 0;  // experiment (results WRONG): the first item twice, the first pass without stores -- the second pass shows the warm timings
+        bool dry_ = (SP4_PROF & 256) != 0;  // experiment (results WRONG): the first item twice, the first pass without stores -- the second pass shows the warm timings
 #endif
         // -B^+ and B^- of this thread's positions (slice tickets: kept across the slices of one visit)
         double bpr[NSP][2], bmr[NSP][2];
@@ -889,7 +921,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
             };
             {
                 int cbeg = c0, cend = c0 + nce;
-                if (p.compact) {  // unique blocks only: the piece that holds column 0 writes the single copy
+                if (SP4_COMPACT) {  // unique blocks only: the piece that holds column 0 writes the single copy
                     cbeg = 0;
                     cend = (c0 == 0) ? 1 : 0;
                 }
@@ -897,7 +929,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
                 // last column stays there, its B^- block goes to the second slice -- 27 blocks each instead of 28 and 26: 0.2-0.35 us of a
                 // 28-32 us launch (v4_flags & 32 switches it off)
                 int half_col = -1;  // the column whose two blocks are shared between the interval's two slices
-                if (!(p.v4_flags & 32) && !p.contig && !p.compact && !tick && p.S == 2 && (d & 1)) {
+                if (!(SP4_FLAGS & 32) && !SP4_CONTIG && !SP4_COMPACT && !tick && p.S == 2 && (d & 1)) {
                     half_col = p.nc - 1;
                     if (c0 > 0) cbeg = half_col;
                 }
@@ -930,7 +962,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
                             if (j < n && sm_) store2(o + blk + n * j, bmr[r][0], bmr[r][1], nt_b);
                         }
                     }
-                    if (!(p.v4_flags & 2)) try_tails(false);
+                    if (!(SP4_FLAGS & 2)) try_tails(false);
 #ifdef PCL_PROFILE
                     if ((p.prof & 128) && cq < cbeg + 2) SP4_STAMP();
 #endif
@@ -1102,6 +1134,7 @@ extern "C" __global__ __launch_bounds__(64 * (SP4_NWAVES + 1)) void pcl_fused_sp
 }
 #endif
 
+#if !SP4_ONE_ITEM  // (the one-item module is the fused kernel alone)
 // ------------------------------------------------------------------------------------------------------------------------------
 // Residual only (what the solver calls in every line-search trial), any order: delta = W_0 of the recursion above, q products.
 // One WAVE per interval and no cooperation between waves (SP4E_NW independent waves per workgroup, three tiles each: D, S, W):
@@ -1298,3 +1331,4 @@ extern "C" __global__ __launch_bounds__(64 * SP4_NPART) void pcl_eval_sparse4c_k
     }
 }
 #endif
+#endif  // !SP4_ONE_ITEM

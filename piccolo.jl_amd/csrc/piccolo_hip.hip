@@ -156,6 +156,10 @@ struct pcl_ctx {
     double *dv4_tab = nullptr, *dv4_tab_t = nullptr, *dv4_mags = nullptr, *dv4_dcf = nullptr;
     hipFunction_t v4_ft = nullptr;  // the fused kernel of the module WITH the slice-ticket roles (launches of several trajectories)
     int v4_ft_failed = 0;           // ... could not be had: those launches take the static split of v4_f (same bits)
+    hipFunction_t v4_f1 = nullptr;  // the fused kernel of the module of launches with ONE item per workgroup (SP4_ONE_ITEM: one trajectory per launch)
+    int v4_f1_failed = 0;           // ... could not be had: those launches take the general module v4_f (same bits)
+    int64_t opt_v4_one_item = -1;   // -1 auto (every launch the module serves) | 0 the general module | 1 require (a launch it does not serve is an error)
+    int64_t last_v4_one_item = 0;   // the last kernel-4 launch ran the one-item module
     // v4_ticket = -1 (auto), launches of several trajectories: static split or slice tickets, decided PER VALUES ARRAY by timing both on it (the
     // two give the same bits).  The static split's time depends on where the array's pages live (181-228 us per 8 seeds by array and box), the
     // tickets' hardly (193-217): neither wins everywhere.  Per array: 2 untimed launches, then 3 + 3 timed ones alternating (events on the launch
@@ -510,6 +514,10 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (const char *tk = getenv("PCL_V4_TICKET")) {  // default of option "v4_ticket" (A/B of whole programs: -1 auto | 0 static split | 1 slice tickets)
         const long v = strtol(tk, nullptr, 10);
         if (v >= -1 && v <= 1) ctx->opt_v4_ticket = v;
+    }
+    if (const char *oi = getenv("PCL_V4_ONE_ITEM")) {  // default of option "v4_one_item" (A/B of whole programs: -1 auto | 0 general module | 1 require)
+        const long v = strtol(oi, nullptr, 10);
+        if (v >= -1 && v <= 1) ctx->opt_v4_one_item = v;
     }
     if (const char *hp = getenv("PCL_HOST_PATH")) {  // default of option "host_path" (1: full values over PCIe, 2: compact + host expansion)
         const long v = strtol(hp, nullptr, 10);
@@ -1020,8 +1028,8 @@ static void note_order(pcl_ctx *ctx, double theta, bool met) {
 }
 static void set_order(pcl_ctx *ctx, int order, double theta) {
     if (ctx->desc.pade_order != order) {  // (modules are per order: the handles of the previous one are dropped, the modules stay cached)
-        ctx->v4_f = ctx->v4_ft = ctx->v4_feval = ctx->v4_fevalc = ctx->v4_fhess = ctx->v4_fhess2 = ctx->v4_fhessc = ctx->v4_fhessp = nullptr;
-        ctx->v4_failed = ctx->v4_hess_failed = ctx->v4_hessc_failed = ctx->v4_ft_failed = 0;
+        ctx->v4_f = ctx->v4_ft = ctx->v4_f1 = ctx->v4_feval = ctx->v4_fevalc = ctx->v4_fhess = ctx->v4_fhess2 = ctx->v4_fhessc = ctx->v4_fhessp = nullptr;
+        ctx->v4_failed = ctx->v4_hess_failed = ctx->v4_hessc_failed = ctx->v4_ft_failed = ctx->v4_f1_failed = 0;
 #ifdef PCL_LAB
         ctx->res.f = nullptr;  // (the resident module bakes the order in as well)
 #endif
