@@ -342,8 +342,13 @@ static int launch_fused_v4(pcl_ctx *ctx, KParams &p, bool compact, bool want_mer
     // the previous slice's stores are issued -- the front of addresses being written stays tight and the workgroups the memory side
     // serves first take more slices: the time no longer depends on where the values array's pages live.
     const int tick_G = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_v4_group > 0 ? ctx->opt_v4_group : 8, ncu));
+    // (the grid a ticket launch gets -- the round-robin split's, below -- must hold one whole group: the kernel divides by gridDim.x / tick_G.  A launch
+    //  of fewer slices than CUs under a large v4_group had no group at all; it runs the static split now: the same bits)
+    const long long tick_S = std::max<long long>(1, std::min<long long>(d, ncu / std::max<long long>(bk, 1)));
+    const long long tick_nc = ctx->opt_cols_per_slice > 0 ? std::min<long long>(ctx->opt_cols_per_slice, d) : (d + tick_S - 1) / tick_S;
+    const long long tick_grid = std::min<long long>(bk * ((d + tick_nc - 1) / tick_nc), ncu);
     const bool ticket_ok = !ctx->res_capture && !compact && ctx->dv4_tick && !ctx->v4_ft_failed && ctx->opt_grid <= 0 && m + 10 <= 16 && ncu % tick_G == 0 &&
-                           v4_lds_bytes(d, m, np) + 8 * 8 * 128 <= (size_t)ctx->max_lds;
+                           tick_grid >= tick_G && v4_lds_bytes(d, m, np) + 8 * 8 * 128 <= (size_t)ctx->max_lds;
     const bool ticket_auto = ticket_ok && ctx->opt_v4_ticket < 0 && p.q <= 2 && p.contig && ctx->opt_contig < 0 && ctx->opt_cols_per_slice <= 0;
     // auto: which of the two this values array gets (see v4_tune); timed launches are bracketed by events below
     pcl_ctx::V4Tune *tune = nullptr;
