@@ -202,7 +202,8 @@ typedef enum pcl_status {
  *   n <= 64                the ordinary context: the same kernels, the same bits
  *   66 <= n <= 128         a LARGE context; even n for unitary / ket / multi-ket states, any n (odd included) under PCL_STATE_VECTOR
  *   n > 128                PCL_ESHAPE (one n x n LDS tile is all a workgroup's 163,840 B can hold: 132,096 B at n = 128)
- *   PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP or pade_order = PCL_ORDER_EXP: PCL_ENOTIMPL
+ *   PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP or pade_order = PCL_ORDER_EXP: PCL_ENOTIMPL (the exponential constraint: by the second flag
+ *                          PCL_LARGE_EXP, below)
  * -- all decided before the device is touched.  A large context runs one kernel family (pcl_kernel_pade_large.hpp: one LDS tile, the powers of
  * G by column panels, the drives in groups where their chain blocks do not fit beside the tile) at Pade orders 2 .. 10 with
  * shared or per-member G0, both batch modes, the member window, 1 .. d state columns and m = 0 .. 24 drives; values, order and layout are those
@@ -250,6 +251,32 @@ typedef enum pcl_status {
  * "last_hess_kernel" 290 + q after a Hessian launch (q = pade_order / 2). */
 #define PCL_LARGE_N 0x100
 #define PCL_LARGE_MAX_N 128
+
+/* A second pcl_desc.batch_mode flag, beside PCL_LARGE_N: the exponential constraint  delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k  at generator
+ * dimensions 66 .. 128 -- the sizes at which a step most easily outgrows Pade order 10.  Valid only together with PCL_LARGE_N, PCL_BATCH_MEMBERS
+ * or PCL_BATCH_TRAJ, and pade_order = PCL_ORDER_EXP; chosen at creation only, never set on its own; pcl_create strips it as it strips PCL_LARGE_N.
+ *   PCL_LARGE_EXP without PCL_LARGE_N, or with a Pade order or order 0      PCL_EINVAL
+ *   with a variational batch mode                                           PCL_LARGE_N's refusal of those modes
+ *   PCL_LARGE_N with PCL_ORDER_EXP and without this flag                    PCL_ENOTIMPL, as before
+ *   both flags, n <= 64                                                     the ordinary exponential context: the same kernels, the same bits
+ *   both flags, 66 <= n <= 128                                              a LARGE EXPONENTIAL context (even n, or any n under PCL_STATE_VECTOR)
+ *   both flags, n > 128                                                     PCL_ESHAPE
+ * -- all decided before the device is touched.  Such a context runs one kernel (pcl_kernel_large_exp.hpp: one LDS tile, the substepped
+ * degree-18 Taylor polynomial in action form with the derivative carried through it, s' = ceil(|dt| |G|_1) substeps) with shared or
+ * per-member G0, both batch modes, the member window, 1 .. d state columns and m = 0 .. 24 drives.  Values, order, layout and structure are
+ * those of the exponential mode at n <= 64: per interval `cols` copies of -E, the diagonal ones of d delta / d X_{k+1}, then the tails
+ * -L_l X_k and -G E X_k: cols n^2 + x_dim (m + 2) values.  No atomics: every work split and two launches give the same bits, and the
+ * residual-only launch gives the bits of the fused launch's residual.  The cost is linear in s', where the kernels of n <= 64 are logarithmic.
+ * Served: pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev] (host-pointer calls
+ * deliver full values), pcl_set_member_window, streams and sync, options, pcl_deriv_*; and with the option "large_full" = 1 the objective
+ * family and pcl_rollout[_dev], on the kernels of a large Pade context (neither depends on the constraint; the rollout then has the
+ * discretisation of the rows).  PCL_ENOTIMPL, each message naming PCL_LARGE_EXP: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64], the
+ * compact Jacobian trio, the merit / reduce entry points, and the options "exp_hess", "exp_full", "large_hess", "large_reduce" = 1.
+ * pcl_set_order_policy / pcl_set_order_from_trajectory: PCL_EINVAL, as on every exponential context.
+ * Options: "cols_per_slice" caps the state columns per workgroup, "general_slices" sets the least number of workgroups per interval,
+ * "large_exp_drives" caps the drives per workgroup (0 auto; PCL_EINVAL when negative or off such a context).  get_option "pade_order" reads -1,
+ * "last_kernel" 320 after a residual + Jacobian launch and 321 after a residual-only launch. */
+#define PCL_LARGE_EXP 0x200
 
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */

@@ -255,6 +255,78 @@ static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac, int mode =
     return PCL_OK;
 }
 
+// Large exponential kernel (pcl_kernel_large_exp.hpp; contexts created with PCL_LARGE_N | PCL_LARGE_EXP on the exponential constraint).  The plan:
+// LD = n | 1, 64 threads per 16-row tile of G; what the one tile leaves of the LDS is NB column blocks of LD doubles, a third of them (NBW) per
+// buffer, since Y, V and the level's result rotate through three.  A chain unit takes nc state columns (at most 16, one column tile of V; option
+// cols_per_slice sets another cap) and mg drives: nc (1 + mg) columns (V | dV_l), nc without the Jacobian; the slices are evened.  Among the
+// drive-group sizes that leave a column of E beside the chain (option large_exp_drives caps them; each evened over its groups) and, for each,
+// the fewest units that fit and the fewest whose columns of E end with the chain's last 16-column tile, the plan with the shortest launch is
+// taken: ceil(W / 16) tile passes per unit times the rounds of the grid over the CUs; on a tie the fewest passes in all, then the larger
+// group.  Option general_slices: that many units at least.  Every split gives the same bits.
+struct LargeExpPlan {
+    int LD, threads, NB, NBW, sx, nc, mg, ngrp, U, npc, W;
+    size_t lds;
+};
+static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargeExpPlan &P) {
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
+    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    P.NBW = P.NB / 3;
+    const bool drv = jac && m > 0;
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16);
+    P.nc = std::max(1, std::min(nc_cap, (P.NBW - (jac ? 1 : 0)) / (drv ? 2 : 1)));
+    P.sx = (cols + P.nc - 1) / P.nc;
+    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.mg = 0, P.ngrp = 1, P.U = P.sx, P.npc = 0;
+    if (jac) {
+        int mg_fit = drv ? std::max(1, std::min(m, (P.NBW - 1) / P.nc - 1)) : 0;
+        if (drv && ctx->opt_large_exp_drives > 0) mg_fit = (int)std::min<int64_t>(mg_fit, ctx->opt_large_exp_drives);
+        // per group size two candidates: the fewest units that fit, and the fewest whose columns of E end with the chain's last column tile
+        long long best_t = -1, best_p = -1;
+        for (int mg0 = mg_fit; mg0 >= (drv ? 1 : 0); --mg0) {
+            const int ngrp = drv ? (m + mg0 - 1) / mg0 : 1, mg = drv ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            const int cx = P.nc * (1 + mg), npc_max = std::max(1, std::min(n, P.NBW - cx)), npc_16 = std::min(npc_max, 16 * (cx / 16 + 1) - cx);
+            for (int cand = 0; cand < 2; ++cand) {
+                const int npc0 = cand ? npc_16 : npc_max;
+                const int U = std::max(P.sx * ngrp, (n + npc0 - 1) / npc0), npc = (n + U - 1) / U;
+                const long long tiles = (cx + npc + 15) / 16, rounds = (std::max(items, 1LL) * U + ctx->n_cu - 1) / std::max(ctx->n_cu, 1);
+                const long long t = tiles * rounds, passes = tiles * U;  // the launch's time in tile passes; what it occupies
+                if (best_t < 0 || t < best_t || (t == best_t && passes < best_p)) best_t = t, best_p = passes, P.mg = mg, P.ngrp = ngrp, P.U = U;
+            }
+            if (!drv) break;
+        }
+        const int chain_units = P.sx * P.ngrp;
+        if (ctx->opt_general_slices > 0) P.U = (int)std::max<long long>(P.U, std::min<long long>(ctx->opt_general_slices, n));
+        P.npc = (n + P.U - 1) / P.U;
+        P.U = std::max(chain_units, (n + P.npc - 1) / P.npc);  // (no unit without work)
+    }
+    P.W = P.nc * (1 + P.mg) + P.npc;
+    P.lds = (size_t)(fixed + 3LL * P.LD * P.W) * sizeof(double);
+}
+static int launch_large_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
+    LargeExpPlan P;
+    const long long items = (long long)p.batch * p.K;
+    large_exp_plan(ctx, p.n, p.cols, p.m, want_jac, items, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large exponential kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
+    p.LD = P.LD;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    if (p.nt >= 2) p.nt = 0;  // (plain or nontemporal block stores; the hand-written write-through store is kernel 3's and 4's)
+    const long long grid = items * P.U;
+    if (int rc = check_grid(ctx, grid)) return rc;
+    typedef void (*kern_t)(const KParams, const int, const int, const int);
+    const kern_t kern = want_jac ? (kern_t)pcl_large_exp_kernel<true> : (kern_t)pcl_large_exp_kernel<false>;
+    if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 7 : 8, P.lds)) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg, P.npc);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_kernel = want_jac ? 320 : 321;  // the large exponential kernel: residual + Jacobian | residual only
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
 // Pattern-compiled fused residual + Jacobian kernel (pcl_kernel_fused_sparse.hpp; any Pade order): sparse exact-iso generators of
 // a unitary problem whose m + 7 chain tiles fit LDS.  PCL_ENOTIMPL (no error text): not taken, the caller goes on to the others.
 static bool v4_available(const pcl_ctx *ctx) {
@@ -815,6 +887,10 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
+    if (ctx->large_exp) {  // (the compact Jacobian is refused at the entry points: LARGE_NOTIMPL)
+        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP)");
+        return launch_large_exp(ctx, p, want_jac);
+    }
     if (ctx->large) {
         if (compact && !ctx->large_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context created with PCL_LARGE_N");
         if (want_jac && compact) return launch_pade_large(ctx, p, true, PL_COMPACT);

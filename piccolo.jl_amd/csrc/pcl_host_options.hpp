@@ -24,6 +24,7 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     }
     else if (!strcmp(key, "exp_hess")) {  // exponential contexts: serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "exp_hess must be 0 or 1");
+        if (v && ctx->large_exp) return fail(ctx, PCL_ENOTIMPL, "%s = 1 is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP): residual and Jacobian, and by option large_full the objective and the rollout", key);
         if (v && ctx->vexp)
             return fail(ctx, PCL_ENOTIMPL, "exp_hess = 1 is not implemented for a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): the Hessian of the Lagrangian needs third Frechet derivatives of exp; solve with a quasi-Newton Hessian");
         if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_hess = 1 needs a context of the exponential constraint (PCL_ORDER_EXP)");
@@ -32,6 +33,7 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     }
     else if (!strcmp(key, "exp_full")) {  // exponential contexts: serve the compact Jacobian trio, the host expansion and the merit / reduce payload (0: refuse them, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "exp_full must be 0 or 1");
+        if (v && ctx->large_exp) return fail(ctx, PCL_ENOTIMPL, "%s = 1 is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP): residual and Jacobian, and by option large_full the objective and the rollout", key);
         if (v && !ctx->exp) return fail(ctx, PCL_EINVAL, "exp_full = 1 needs a plain context of the exponential constraint (PCL_ORDER_EXP, not a variational one)");
         ctx->exp_full = (int)v;
     }
@@ -49,6 +51,7 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     }
     else if (!strcmp(key, "large_hess")) {  // large contexts (PCL_LARGE_N, n > 64): serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "large_hess must be 0 or 1");
+        if (v && ctx->large_exp) return fail(ctx, PCL_ENOTIMPL, "%s = 1 is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP): residual and Jacobian, and by option large_full the objective and the rollout", key);
         if (v && !ctx->large) return fail(ctx, PCL_EINVAL, "large_hess = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64); every other context has its Hessian options of its own");
         if (v)
             TRY(large_hess_enable(ctx));
@@ -59,10 +62,15 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v < 0 || !ctx->large) return fail(ctx, PCL_EINVAL, "large_hess_drives must be >= 0, on a large context (PCL_LARGE_N, generator dimension above 64)");
         ctx->opt_large_hess_drives = v;
     }
+    else if (!strcmp(key, "large_exp_drives")) {  // large exponential contexts: the most drives per group of the residual + Jacobian launch (0 auto: the group size with the fewest column-tile passes)
+        if (v < 0 || !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_drives must be >= 0, on a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension above 64)");
+        ctx->opt_large_exp_drives = v;
+    }
     else if (!strcmp(key, "large_full")) {  // large contexts: serve the objective family and the rollout (0: refuse them, the default, and drop goal, weights, regularisers)
         TRY(large_set_full(ctx, v));
     }
     else if (!strcmp(key, "large_reduce")) {  // large contexts: serve the compact Jacobian trio, the host calls' compact route and the merit / reduce payload (0: refuse them, the default)
+        if (v == 1 && ctx->large_exp) return fail(ctx, PCL_ENOTIMPL, "%s = 1 is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP): residual and Jacobian, and by option large_full the objective and the rollout", key);
         TRY(large_set_reduce(ctx, v));
     }
     else if (!strcmp(key, "large_rollout_stage")) {  // ... measurements (bench/bench_large_full.py): 0 both launches of the rollout | 1 the propagators only | 2 the chain only
@@ -223,6 +231,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->large_hess;
     else if (!strcmp(key, "large_hess_drives"))
         *v = ctx->opt_large_hess_drives;
+    else if (!strcmp(key, "large_exp_drives"))
+        *v = ctx->opt_large_exp_drives;
     else if (!strcmp(key, "large_full"))
         *v = ctx->large_full;
     else if (!strcmp(key, "large_reduce"))

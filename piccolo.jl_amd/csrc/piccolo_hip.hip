@@ -6,6 +6,7 @@
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
+//   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
 //   pcl_kernels_hessian.hpp    Hessian of the Lagrangian: versions 1 (one workgroup per interval) and 2 (column chunks, fallback)
@@ -51,6 +52,7 @@
 #include "pcl_kernel_pade_large.hpp"
 #include "pcl_kernel_pade_large_hess.hpp"
 #include "pcl_kernel_large_rollout.hpp"
+#include "pcl_kernel_large_exp.hpp"
 #include "pcl_kernels_fused_v2.hpp"
 #include "pcl_kernel_fused_v3.hpp"
 #include "pcl_kernel_eval.hpp"
@@ -81,6 +83,8 @@ struct pcl_ctx {
     int large_reduce = 0;                  // ... option large_reduce: the compact Jacobian trio, the host calls' compact route and the merit / reduce payload are served (the modes of pcl_kernel_pade_large.hpp, pcl_expand_large_kernel)
     int64_t opt_large_rollout_stage = 0;   // ... ... measurements: 0 both launches of the rollout | 1 the propagators only | 2 the chain only, on the workspace as it stands
     double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
+    int large_exp = 0;                     // ... PCL_LARGE_EXP with PCL_ORDER_EXP (then `large` and `exp` are set too): every residual / Jacobian launch is pcl_large_exp_kernel (pcl_kernel_large_exp.hpp); large_full serves the objective and the rollout, everything else is refused
+    int64_t opt_large_exp_drives = 0;      // ... ... the most drives per group of that launch (0 auto)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
     int exp_full = 0;            // ... option exp_full: the compact Jacobian trio, the host expansion and the merit / reduce payload are served
@@ -397,9 +401,12 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
     } while (0)
 
 // A large context (PCL_LARGE_N, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is refused in these words
-// (the Hessian of the Lagrangian, the objective family and the rollout unless their options are on: the gates below).
+// (the Hessian of the Lagrangian, the objective family and the rollout unless their options are on: the gates below).  A large exponential
+// context (PCL_LARGE_EXP) has the option large_full alone: its refusals name that flag.
 #define LARGE_NOTIMPL(ctx, what)                                                                                                                          \
     do {                                                                                                                                                  \
+        if ((ctx) && (ctx)->large_exp)                                                                                                                    \
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension %d > 64): residual and Jacobian, and by option large_full the objective and the rollout", what, (ctx)->n); \
         if ((ctx) && (ctx)->large)                                                                                                                        \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
     } while (0)
@@ -439,17 +446,22 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
-    // PCL_LARGE_N: stripped here, once; everything below (and the context) sees the plain batch mode
+    // PCL_LARGE_N and PCL_LARGE_EXP: stripped here, once; everything below (and the context) sees the plain batch mode
     const bool large_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_N) != 0;
+    const bool large_exp_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_EXP) != 0;
     pcl_desc plain_desc = *dsc;
-    if (large_flag) {
-        plain_desc.batch_mode &= ~PCL_LARGE_N;
+    if (large_flag || large_exp_flag) {
+        plain_desc.batch_mode &= ~(PCL_LARGE_N | PCL_LARGE_EXP);
         dsc = &plain_desc;
+        if (large_exp_flag && !large_flag)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_EXP goes with PCL_LARGE_N (batch_mode | PCL_LARGE_N | PCL_LARGE_EXP, pade_order = PCL_ORDER_EXP)");
         if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP)
             return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the variational integrators (batch_mode %s); it goes with PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ",
                         dsc->batch_mode == PCL_BATCH_VARIATIONAL ? "PCL_BATCH_VARIATIONAL" : "PCL_BATCH_VARIATIONAL_EXP");
-        if (dsc->pade_order == PCL_ORDER_EXP)
-            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the exponential constraint (pade_order = PCL_ORDER_EXP); it serves the diagonal Pade orders 2 .. 10");
+        if (large_exp_flag && dsc->pade_order != PCL_ORDER_EXP)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_EXP is the exponential constraint at generator dimensions 66 .. %d: it needs pade_order = PCL_ORDER_EXP (got %d)", PCL_LARGE_MAX_N, dsc->pade_order);
+        if (dsc->pade_order == PCL_ORDER_EXP && !large_exp_flag)
+            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the exponential constraint (pade_order = PCL_ORDER_EXP); it serves the diagonal Pade orders 2 .. 10 -- and that constraint by the flag PCL_LARGE_EXP beside it");
     }
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL && dsc->pade_order == PCL_ORDER_EXP)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented; use batch_mode = PCL_BATCH_VARIATIONAL_EXP");
@@ -502,6 +514,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     ctx->cols = cols;
     ctx->vec = vec ? 1 : 0;
     ctx->large = large ? 1 : 0;
+    ctx->large_exp = large && large_exp_flag ? 1 : 0;
     ctx->exp = dsc->pade_order == PCL_ORDER_EXP ? 1 : 0;
     ctx->x_offs.assign(dsc->x_offs, dsc->x_offs + n_off);
     ctx->hG0.assign(dsc->G0, dsc->G0 + (size_t)n * n * (dsc->per_member_G0 ? dsc->batch : 1));
@@ -679,7 +692,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     }
     std::vector<double> g0(dsc->G0, dsc->G0 + nn * (dsc->per_member_G0 ? dsc->batch : 1));
     CREATE_TRY(upload(ctx, &ctx->dG0, g0));
-    if ((n <= 16 || ctx->exp) && m >= 1) {  // (... and the exponential mode at every n: the directions of its Frechet pairs)
+    if ((n <= 16 || (ctx->exp && !ctx->large_exp)) && m >= 1) {  // (... and the exponential mode at every n <= 64: the directions of its Frechet pairs)
         std::vector<double> gjd(dsc->Gj, dsc->Gj + nn * m);
         CREATE_TRY(upload(ctx, &ctx->dGjd, gjd));
     }

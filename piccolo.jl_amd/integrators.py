@@ -92,16 +92,17 @@ def _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode=
         raise ValueError("large_hessian=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
 
 
-def _check_large_full(large_full, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+def _check_large_full(large_full, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS, large_exp=False):
     """The keyword ``large_full`` (the library's option of that name: the objective family and the rollout at generator dimensions 66 .. 128) goes
-    with ``large_generator=True`` on the Pade constraint of a plain context: anything else is a ``ValueError``, before any device call."""
+    with ``large_generator=True`` on the Pade constraint of a plain context -- or on the exponential constraint beside ``large_exp=True``:
+    anything else is a ``ValueError``, before any device call."""
     if not large_full:
         return
     if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
         raise ValueError("large_full=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)")
     if not large_generator:
         raise ValueError("large_full=True is the objective and the rollout of a context created with large_generator=True: it needs that keyword")
-    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP:
+    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP and not large_exp:
         raise ValueError("large_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
 
 
@@ -119,14 +120,28 @@ def _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode=PC
         raise ValueError("large_reduce=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
 
 
+def _check_large_exp(large_exp, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_exp`` (the library's flag ``PCL_LARGE_EXP``: the exponential constraint at generator dimensions 66 .. 128) goes with
+    ``large_generator=True`` and ``pade_order="exp"`` on a plain context: anything else is a ``ValueError``, before any device call."""
+    if not large_exp:
+        return
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("large_exp=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)")
+    if not large_generator:
+        raise ValueError("large_exp=True is the exponential constraint of a context created with large_generator=True: it needs that keyword")
+    if _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
+        raise ValueError("large_exp=True is the exponential constraint at generator dimensions 66 .. 128: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
-                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False):  # fmt: skip
+                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):  # fmt: skip
+        _check_large_exp(large_exp, large_generator, pade_order, batch_mode)
         _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
-        _check_large_full(large_full, large_generator, pade_order, batch_mode)
+        _check_large_full(large_full, large_generator, pade_order, batch_mode, large_exp)
         _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         exp_hessian = _exp_hessian_value(exp_hessian)
@@ -149,7 +164,7 @@ class _PclContext:
         xo = np.ascontiguousarray(np.asarray(x_offs, dtype=np.int32).reshape(-1))
         desc = _lib.pcl_desc(
             struct_size=ctypes.sizeof(_lib.pcl_desc), d=d, n_drives=m, N=N, z_dim=z_dim, u_off=u_off, dt_off=dt_off,
-            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0), pade_order=pade_order, device_id=device,
+            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0) | (_lib.PCL_LARGE_EXP if large_exp else 0), pade_order=pade_order, device_id=device,
             index_base=index_base, per_member_G0=int(bool(per_member_G0)), state_cols=state_cols, global_dim=global_dim,
             G0=g0.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
             Gj=gj.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
@@ -181,6 +196,9 @@ class _PclContext:
         # objective unless ``large_full`` switches the library's option of that name on).  At n <= 64 the
         # flag changes nothing.  ``large_hessian`` switches the library's option large_hess on there: hess_nnz / hess_per follow it (set_option)
         self.large = bool(large_generator) and n > 64
+        # ``large_exp`` (the flag PCL_LARGE_EXP beside it, pade_order "exp"): residual and Jacobian of the exponential constraint there, the
+        # objective and the rollout by ``large_full``; the Hessian of the Lagrangian, the compact Jacobian and the payload raise
+        self.large_exp = bool(large_exp) and self.large
         self.large_hessian = False
         self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
         self.large_reduce = False  # (``large_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
@@ -612,7 +630,7 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False):
+                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -628,7 +646,7 @@ class HipPadeIntegrator:
         ``large_generator=True`` sets the library's flag ``PCL_LARGE_N``: generator dimensions 66 .. 128 (a transmon with a cavity, density vectors of
         9 .. 11 levels) on the Pade constraint, residual and Jacobian only -- ``hessian_structure`` / ``eval_hessian_of_lagrangian``, the rollout and the
         objective raise (see ``large_hessian`` and ``large_full`` below); solve with a quasi-Newton Hessian.  Never set on its own: without it such a system is refused as before.  With
-        ``pade_order="exp"`` the library refuses it.  At a dimension up to 64 it changes nothing.
+        ``pade_order="exp"`` the library refuses it unless ``large_exp=True`` is set as well (below).  At a dimension up to 64 it changes nothing.
         ``large_hessian=True`` (with ``large_generator=True`` on the Pade constraint only, else ``ValueError``): the Hessian of the Lagrangian is served at
         those dimensions too (the library's option ``large_hess``) -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work.  At a dimension up to
         64 the ordinary context serves its Hessian as always.
@@ -638,9 +656,15 @@ class HipPadeIntegrator:
         ``large_reduce=True`` (the same conditions, else ``ValueError``): the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``, ``eval_jac_compact_dev``,
         ``jac_expand_dev``), the host-pointer calls' compact route and the merit / reduce payload (``merit_grad_dev``, ``eval_jac_merit_dev`` -- with
         ``vals=None`` the payload alone -- and, together with ``large_full``, ``eval_jac_merit_objective_dev``) are served at those dimensions too (the
-        library's option ``large_reduce``).  Independent of the other two; at a dimension up to 64 the ordinary context serves them as always."""
+        library's option ``large_reduce``).  Independent of the other two; at a dimension up to 64 the ordinary context serves them as always.
+        ``large_exp=True`` (with ``large_generator=True`` and ``pade_order="exp"`` only, else ``ValueError``) sets the library's second flag
+        ``PCL_LARGE_EXP``: the exponential constraint at generator dimensions 66 .. 128, residual and exact Jacobian (a substepped Taylor polynomial,
+        ``ceil(|dt| |G|_1)`` substeps: the cost is linear in the step).  ``large_full=True`` is allowed beside it (objective and rollout);
+        ``large_hessian``, ``large_reduce``, ``exp_hessian`` and ``exp_full`` are not: solve with a quasi-Newton Hessian.  Never set on its own;
+        at a dimension up to 64 the ordinary exponential context serves the constraint as always."""
+        _check_large_exp(large_exp, large_generator, pade_order)
         _check_large_hessian(large_hessian, large_generator, pade_order)
-        _check_large_full(large_full, large_generator, pade_order)
+        _check_large_full(large_full, large_generator, pade_order, PCL_BATCH_MEMBERS, large_exp)
         _check_large_reduce(large_reduce, large_generator, pade_order)
         exp_hessian = _exp_hessian_value(exp_hessian)
         _check_exp_full(exp_full, pade_order)
@@ -685,9 +709,10 @@ class HipPadeIntegrator:
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
             state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
-            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
+            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce, large_exp=large_exp,
         )  # fmt: skip
         self._large_generator = bool(large_generator)
+        self._large_exp = bool(large_exp)
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
         self._state_cols = _lib.PCL_STATE_VECTOR if vec else cols
@@ -716,7 +741,7 @@ class HipPadeIntegrator:
             raise NotImplementedError("f is defined for single-state integrators")
         if self._f_ctx is None:
             self._f_ctx = _PclContext(d=c.d, m=c.m, N=2, z_dim=c.x_dim + 1 + c.m, u_off=c.x_dim + 1, dt_off=c.x_dim,
-                                      x_offs=[0], G0=self.G_drift, Gj=self.G_drives, batch=1, large_generator=self._large_generator,
+                                      x_offs=[0], G0=self.G_drift, Gj=self.G_drives, batch=1, large_generator=self._large_generator, large_exp=self._large_exp,
                                       batch_mode=PCL_BATCH_MEMBERS, state_cols=self._state_cols, pade_order=_resolved_order(c))  # fmt: skip
         z = np.zeros((2, c.x_dim + 1 + c.m))
         z[0, : c.x_dim], z[0, c.x_dim], z[0, c.x_dim + 1 :] = x, dt, np.asarray(u)[: c.m]
@@ -749,7 +774,8 @@ class HipVariationalIntegrator:
     path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False):
+                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):
+        _check_large_exp(large_exp, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_reduce(large_reduce, False, pade_order, PCL_BATCH_VARIATIONAL)

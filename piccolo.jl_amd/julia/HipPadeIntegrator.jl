@@ -86,7 +86,14 @@ end
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
                       exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
-                      large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false)
+                      large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false)
+    # large_exp = true (with large_generator = true and pade_order = :exp only): the library's second flag PCL_LARGE_EXP in batch_mode -- the
+    # exponential constraint at generator dimensions 66 .. 128, residual and exact Jacobian (hess_per = 0: solve with eval_hessian = false).
+    # large_full = true is allowed beside it; the other large options and the exponential ones are refused by the library.  Never set on its own.
+    (large_exp && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_exp = true is the exponential constraint of a context created with large_generator = true: it needs that keyword"))
+    (large_exp && pade_order != PCL_ORDER_EXP) &&
+        throw(ArgumentError("HipPadeIntegrator: large_exp = true is the exponential constraint at generator dimensions 66 .. 128: it needs pade_order = :exp"))
     # large_reduce = true (the same conditions): the library's option large_reduce -- pcl_jac_compact_nnz, pcl_eval_jac_compact_dev, pcl_jac_expand_dev,
     # the host-pointer calls' compact route and the merit / reduce entry points are served at those dimensions too.  Independent of the other two.
     (large_reduce && !large_generator) &&
@@ -97,7 +104,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     # and pcl_rollout* are served at those dimensions too.  Independent of large_hessian; at n <= 64 the ordinary context serves them as always.
     (large_full && !large_generator) &&
         throw(ArgumentError("HipPadeIntegrator: large_full = true is the objective and the rollout of a context created with large_generator = true: it needs that keyword"))
-    (large_full && pade_order == PCL_ORDER_EXP) &&
+    (large_full && pade_order == PCL_ORDER_EXP && !large_exp) &&
         throw(ArgumentError("HipPadeIntegrator: large_full = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large contexts"))
     # large_hessian = true (with large_generator = true on the Pade constraint only): the library's option large_hess -- the Hessian of the
     # Lagrangian at those dimensions too (hess_per > 0, eval_hessian = true works).  At n <= 64 the ordinary context serves its Hessian as always.
@@ -119,7 +126,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve G0 Gj x_offs begin
         desc = PclDesc(sizeof(PclDesc), d, m, N, z_dim, u_off, dt_off,
-                       length(x_offs), (large_generator ? PCL_LARGE_N : 0) #= PCL_BATCH_MEMBERS [| PCL_LARGE_N] =#, pade_order #= 2, 4, 6, 8 or 10 =#, device, 1 #= 1-based =#,
+                       length(x_offs), (large_generator ? PCL_LARGE_N : 0) | (large_exp ? PCL_LARGE_EXP : 0) #= PCL_BATCH_MEMBERS [| PCL_LARGE_N [| PCL_LARGE_EXP]] =#, pade_order #= 2, 4, 6, 8 or 10 =#, device, 1 #= 1-based =#,
                        length(G0s) > 1 ? 1 : 0, state_cols, global_dim,
                        pointer(G0), pointer(Gj), pointer(x_offs))
         rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
@@ -208,6 +215,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
+const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -307,7 +315,8 @@ end
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false)
+                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false)
+    large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_reduce && throw(ArgumentError("HipPadeIntegrator: large_reduce = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)"))
     large_full && throw(ArgumentError("HipPadeIntegrator: large_full = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)"))
     large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
