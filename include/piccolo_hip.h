@@ -275,7 +275,17 @@ typedef enum pcl_status {
  * pcl_set_order_policy / pcl_set_order_from_trajectory: PCL_EINVAL, as on every exponential context.
  * Options: "cols_per_slice" caps the state columns per workgroup, "general_slices" sets the least number of workgroups per interval,
  * "large_exp_drives" caps the drives per workgroup (0 auto; PCL_EINVAL when negative or off such a context).  get_option "pade_order" reads -1,
- * "last_kernel" 320 after a residual + Jacobian launch and 321 after a residual-only launch. */
+ * "last_kernel" 320 after a residual + Jacobian launch and 321 after a residual-only launch.
+ * Option "large_exp_hess" (default 0, never on by itself; 1 on any other context and any value but 0 and 1: PCL_EINVAL; it reads 0 everywhere
+ * else): at 1 pcl_hess, pcl_hess_dev, pcl_hess_nnz and pcl_hess_structure[_i64] are served -- values, order and structure are those of the option
+ * "exp_hess" at n <= 62: per interval (m + 1)(m + 2) / 2 + x_dim (m + 1) values [(u_i,u_l), l <= i | (dt,u_l) | (dt,dt) | (u_l,X_k) | (dt,X_k)].
+ * pcl_kernel_large_exp_hess.hpp: the adjoint of the Jacobian's substepped recurrence on G^T, started from the multipliers, with the second
+ * derivative carried; one workgroup per (interval, slice of state columns, pair of drive groups), per-column partial sums in a
+ * workspace (allocated when the option is first set to 1, freed by pcl_destroy) added in column order by a second launch on the same stream: no
+ * atomics, every work split, two launches and both pointer paths give the same bits.  Back at 0 the refusals return, in the same words; the
+ * compact trio, the merit / reduce entry points and the options "exp_hess", "large_hess" = 1 stay refused at either value.
+ * "large_exp_hess_drives" caps the drives per group of that launch (0 auto; PCL_EINVAL when negative or off such a context), "cols_per_slice"
+ * its state columns per workgroup; get_option "last_hess_kernel" reads 320 after it. */
 #define PCL_LARGE_EXP 0x200
 
 typedef struct pcl_desc {

@@ -76,6 +76,87 @@ static int launch_pade_large_hess(pcl_ctx *ctx, const double *Z, const double *m
     return PCL_OK;
 }
 
+// Hessian of the Lagrangian of a large exponential context (pcl_kernel_large_exp_hess.hpp; option large_exp_hess).  The plan, next to
+// large_exp_plan (pcl_host_launch_pade.hpp): LD = n | 1, 64 threads per 16-row tile; what the tile leaves of the LDS is NB column blocks of LD
+// doubles, a third of them (NBW) per rotating buffer.  A unit of nc state columns and a pair of drive groups of mg drives holds, per state column,
+// W, the dW of its drives and the d2W of its pairs: Td = 1 + mg + mg (mg + 1) / 2 columns on the diagonal, To = 1 + 2 mg + mg^2 off it.  Wherever
+// there is more than one group the buffer is sized by the OFF-DIAGONAL count (n = 120, 15 columns: mg = 2; mg = 3 would fit a diagonal unit and
+// not an off-diagonal one); one group has its diagonal unit alone and is sized by Td; no drives: two columns ([X_k | G X_k] behind the chain).
+// Among the slice widths nc <= 16 (option cols_per_slice > 0: that width, or the widest that fits) and the group sizes (option
+// large_exp_hess_drives caps them; each evened over its groups) that fit, the plan with the fewest 16-column tile passes per interval is taken,
+//     sx (ngrp ceil(nc Td / 16) + ngrp (ngrp - 1) / 2 ceil(nc To / 16)),
+// on a tie the fewest units, then the wider slice and the larger group.  U = sx ngrp (ngrp + 1) / 2 units per interval.  The smallest unit needs
+// 4 columns per buffer; n = 128 has 9, so nothing is refused for m <= 24, n <= 128.  Every split gives the same bits.
+struct LargeExpHessPlan {
+    int LD, threads, NB, NBW, sx, nc, mg, ngrp, U, W;
+    long long passes;
+    size_t lds;
+};
+static void large_exp_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeExpHessPlan &P) {
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
+    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    P.NBW = P.NB / 3;
+    const int t_min = m == 0 ? 2 : (m == 1 ? 3 : 4);  // the narrowest unit: no drives | one drive | two groups of one
+    const int nc_fit = std::max(1, P.NBW / t_min);
+    const int nc_hi = std::min(nc_fit, ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16));
+    const int nc_lo = ctx->opt_cols_per_slice > 0 ? nc_hi : 1;
+    const int mg_cap = m > 0 ? (ctx->opt_large_exp_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_exp_hess_drives, m) : m) : 0;
+    long long best_p = -1, best_u = -1;
+    P.sx = cols, P.nc = 1, P.mg = m > 0 ? 1 : 0, P.ngrp = std::max(m, 1), P.W = t_min;
+    for (int nc0 = nc_hi; nc0 >= nc_lo; --nc0) {
+        const int sx = (cols + nc0 - 1) / nc0, nc = (cols + sx - 1) / sx;  // even slices
+        for (int mg0 = mg_cap; mg0 >= (m > 0 ? 1 : 0); --mg0) {
+            const int ngrp = m > 0 ? (m + mg0 - 1) / mg0 : 1, mg = m > 0 ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            const int Td = m > 0 ? 1 + mg + mg * (mg + 1) / 2 : 2, To = 1 + 2 * mg + mg * mg;
+            const int W = nc * (ngrp > 1 ? To : Td);
+            if (W > P.NBW) continue;
+            const long long npo = (long long)ngrp * (ngrp - 1) / 2;
+            const long long passes = sx * (ngrp * (long long)((nc * (m > 0 ? Td : 1) + 15) / 16) + npo * ((nc * To + 15) / 16)), units = sx * (ngrp + npo);
+            if (best_p < 0 || passes < best_p || (passes == best_p && units < best_u)) best_p = passes, best_u = units, P.sx = sx, P.nc = nc, P.mg = mg, P.ngrp = ngrp, P.W = W;
+            if (m == 0) break;
+        }
+    }
+    P.passes = best_p;
+    P.U = P.sx * (P.ngrp * (P.ngrp + 1) / 2);
+    P.lds = (size_t)(fixed + 3LL * P.LD * P.W) * sizeof(double);
+}
+static int large_exp_hess_enable(pcl_ctx *ctx) {
+    if (!ctx->dlehpart) {
+        ON_DEVICE(ctx);
+        const long long m = ctx->desc.n_drives;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->dlehpart, (size_t)ctx->desc.batch * ctx->K * ctx->cols * ((m + 1) * (m + 2) / 2) * sizeof(double)));
+    }
+    ctx->large_exp_hess = 1;
+    return PCL_OK;
+}
+static int launch_large_exp_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    KParams p;
+    fill_params(ctx, p);
+    p.Z = window_Z(ctx, Z);
+    p.mu = mu;
+    p.hess = hess;
+    p.hpart = ctx->dlehpart;
+    LargeExpHessPlan P;
+    large_exp_hess_plan(ctx, p.n, p.cols, p.m, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large exponential Hessian kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
+    p.LD = P.LD;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    const long long items = (long long)p.batch * p.K, grid = items * P.U;
+    if (int rc = check_grid(ctx, grid)) return rc;
+    if (int rc = set_lds_attr(ctx, (const void *)pcl_large_exp_hess_kernel, 9, P.lds)) return rc;
+    hipLaunchKernelGGL(pcl_large_exp_hess_kernel, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg, P.ngrp, P.W);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(pcl_large_exp_hess_sum_kernel, dim3((unsigned)items), dim3(256), 0, ctx->stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_hess_kernel = 320;  // the large exponential Hessian kernel
+    return PCL_OK;
+}
+
 // The Hessian of the Lagrangian in the exponential mode (option exp_hess; pcl_kernel_exp_hess.hpp): five rotating n x n tiles and the
 // reduction words; G(u_k) takes a sixth tile where that fits.  *g_lds: whether it does.  Returns the bytes of LDS the kernel needs.
 static size_t exp_hess_lds_bytes(const pcl_ctx *ctx, int *g_lds) {
@@ -441,6 +522,7 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
     LARGE_HESS_GATE(ctx, "pcl_hess");
+    if (ctx->large_exp) return launch_large_exp_hess(ctx, Z, mu, hess);
     if (ctx->large) return launch_pade_large_hess(ctx, Z, mu, hess);
     VAR_EXP_NOHESS(ctx, "pcl_hess");
     EXP_HESS_GATE(ctx, "pcl_hess");

@@ -66,6 +66,18 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v < 0 || !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_drives must be >= 0, on a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension above 64)");
         ctx->opt_large_exp_drives = v;
     }
+    else if (!strcmp(key, "large_exp_hess")) {  // large exponential contexts: serve the Hessian of the Lagrangian (0: refuse it, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "large_exp_hess must be 0 or 1");
+        if (v && !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_hess = 1 needs a large exponential context (batch_mode | PCL_LARGE_N | PCL_LARGE_EXP, pade_order = PCL_ORDER_EXP, at a generator dimension above 64); every other context has its Hessian options of its own");
+        if (v)
+            TRY(large_exp_hess_enable(ctx));
+        else
+            ctx->large_exp_hess = 0;
+    }
+    else if (!strcmp(key, "large_exp_hess_drives")) {  // ... the most drives per group of that launch (0 auto: as many as fit; capped by what fits)
+        if (v < 0 || !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_hess_drives must be >= 0, on a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension above 64)");
+        ctx->opt_large_exp_hess_drives = v;
+    }
     else if (!strcmp(key, "large_full")) {  // large contexts: serve the objective family and the rollout (0: refuse them, the default, and drop goal, weights, regularisers)
         TRY(large_set_full(ctx, v));
     }
@@ -233,6 +245,10 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->opt_large_hess_drives;
     else if (!strcmp(key, "large_exp_drives"))
         *v = ctx->opt_large_exp_drives;
+    else if (!strcmp(key, "large_exp_hess"))
+        *v = ctx->large_exp_hess;
+    else if (!strcmp(key, "large_exp_hess_drives"))
+        *v = ctx->opt_large_exp_hess_drives;
     else if (!strcmp(key, "large_full"))
         *v = ctx->large_full;
     else if (!strcmp(key, "large_reduce"))

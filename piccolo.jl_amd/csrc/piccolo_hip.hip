@@ -6,6 +6,7 @@
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
+//   pcl_kernel_large_exp_hess.hpp   ... its Hessian of the Lagrangian (option large_exp_hess): the adjoint of that recurrence with the second derivative carried, per-column partial sums
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
@@ -53,6 +54,7 @@
 #include "pcl_kernel_pade_large_hess.hpp"
 #include "pcl_kernel_large_rollout.hpp"
 #include "pcl_kernel_large_exp.hpp"
+#include "pcl_kernel_large_exp_hess.hpp"
 #include "pcl_kernels_fused_v2.hpp"
 #include "pcl_kernel_fused_v3.hpp"
 #include "pcl_kernel_eval.hpp"
@@ -85,6 +87,9 @@ struct pcl_ctx {
     double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
     int large_exp = 0;                     // ... PCL_LARGE_EXP with PCL_ORDER_EXP (then `large` and `exp` are set too): every residual / Jacobian launch is pcl_large_exp_kernel (pcl_kernel_large_exp.hpp); large_full serves the objective and the rollout, everything else is refused
     int64_t opt_large_exp_drives = 0;      // ... ... the most drives per group of that launch (0 auto)
+    int large_exp_hess = 0;                // ... ... option large_exp_hess: its Hessian of the Lagrangian is served (pcl_kernel_large_exp_hess.hpp)
+    int64_t opt_large_exp_hess_drives = 0; // ... ... ... the most drives per group of that launch (0 auto: as many as fit)
+    double *dlehpart = nullptr;            // ... ... ... its workspace: per (member, interval, state column) the (m + 1)(m + 2) / 2 partial sums (allocated when the option is first set to 1)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
     int exp_full = 0;            // ... option exp_full: the compact Jacobian trio, the host expansion and the merit / reduce payload are served
@@ -411,10 +416,11 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
     } while (0)
 
-// ... its Hessian of the Lagrangian by option large_hess only (pcl_kernel_pade_large_hess.hpp): without it, the same words
+// ... its Hessian of the Lagrangian by option large_hess only (pcl_kernel_pade_large_hess.hpp; a large exponential context: by option large_exp_hess,
+// pcl_kernel_large_exp_hess.hpp): without it, the same words
 #define LARGE_HESS_GATE(ctx, what)                                \
     do {                                                          \
-        if ((ctx) && !(ctx)->large_hess) LARGE_NOTIMPL(ctx, what); \
+        if ((ctx) && !(ctx)->large_hess && !(ctx)->large_exp_hess) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
 // ... and the objective family and the rollout by option large_full only (pcl_kernel_large_rollout.hpp): without it, the same words
@@ -431,7 +437,7 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 
 #define EXP_HESS_GATE(ctx, what)                       \
     do {                                               \
-        if ((ctx) && !(ctx)->exp_hess) EXP_NOTIMPL(ctx, what); \
+        if ((ctx) && !(ctx)->exp_hess && !(ctx)->large_exp_hess) EXP_NOTIMPL(ctx, what); \
     } while (0)
 // ... and the compact Jacobian trio and the merit / reduce entry points unless its option exp_full is on
 #define EXP_FULL_GATE(ctx, what)                       \
@@ -768,7 +774,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);

@@ -133,12 +133,26 @@ def _check_large_exp(large_exp, large_generator, pade_order, batch_mode=PCL_BATC
         raise ValueError("large_exp=True is the exponential constraint at generator dimensions 66 .. 128: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
 
 
+def _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_exp_hessian`` (the library's option ``large_exp_hess``: the Hessian of the Lagrangian of the exponential constraint at
+    generator dimensions 66 .. 128) goes with ``large_exp=True`` -- and hence ``large_generator=True`` and ``pade_order="exp"`` -- on a plain
+    context: anything else is a ``ValueError``, before any device call."""
+    if not large_exp_hessian:
+        return
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("large_exp_hessian=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)")
+    if not large_exp:
+        raise ValueError("large_exp_hessian=True is the Hessian of the Lagrangian of a context created with large_exp=True "
+                         "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
-                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):  # fmt: skip
+                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False):  # fmt: skip
+        _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode)
         _check_large_exp(large_exp, large_generator, pade_order, batch_mode)
         _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
         _check_large_full(large_full, large_generator, pade_order, batch_mode, large_exp)
@@ -199,6 +213,7 @@ class _PclContext:
         # ``large_exp`` (the flag PCL_LARGE_EXP beside it, pade_order "exp"): residual and Jacobian of the exponential constraint there, the
         # objective and the rollout by ``large_full``; the Hessian of the Lagrangian, the compact Jacobian and the payload raise
         self.large_exp = bool(large_exp) and self.large
+        self.large_exp_hessian = False  # (``large_exp_hessian`` switches the library's option large_exp_hess on there: hess_nnz / hess_per follow it, set_option)
         self.large_hessian = False
         self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
         self.large_reduce = False  # (``large_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
@@ -208,6 +223,8 @@ class _PclContext:
             self.set_option("var_exp_hess" if batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess", 1)
         if large_hessian and self.large:  # (at n <= 64 the ordinary context serves its Hessian as always: the option is not set)
             self.set_option("large_hess", 1)
+        elif large_exp_hessian and self.large_exp:  # (at n <= 64 ``exp_hessian`` is the ordinary exponential context's switch: the option is not set)
+            self.set_option("large_exp_hess", 1)
         elif (self.exponential and not self.exp_hessian) or self.large:
             self.hess_nnz = self.hess_per = 0
         else:
@@ -373,8 +390,8 @@ class _PclContext:
         if self.exp_hessian:
             self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz = a.value
-        if self.large:  # (the compact Jacobian by ``large_reduce`` only; the Hessian of the Lagrangian by ``large_hessian`` only)
-            if self.large_hessian:
+        if self.large:  # (the compact Jacobian by ``large_reduce`` only; the Hessian of the Lagrangian by ``large_hessian`` / ``large_exp_hessian`` only)
+            if self.large_hessian or self.large_exp_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
                 self.hess_nnz = a.value
             if self.large_reduce:
@@ -554,6 +571,12 @@ class _PclContext:
             if self.large_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.hess_nnz, self.hess_per = a.value, b.value
+        if self.large_exp and key == "large_exp_hess":  # ... and on a large exponential context
+            self.large_exp_hessian = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.large_exp_hessian:
+                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.hess_nnz, self.hess_per = a.value, b.value
         if self.large and key == "large_full":
             self.large_full = bool(value)
         if self.large and key == "large_reduce":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
@@ -630,7 +653,8 @@ class HipPadeIntegrator:
     """
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):
+                 exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
+                 large_exp_hessian=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -660,8 +684,14 @@ class HipPadeIntegrator:
         ``large_exp=True`` (with ``large_generator=True`` and ``pade_order="exp"`` only, else ``ValueError``) sets the library's second flag
         ``PCL_LARGE_EXP``: the exponential constraint at generator dimensions 66 .. 128, residual and exact Jacobian (a substepped Taylor polynomial,
         ``ceil(|dt| |G|_1)`` substeps: the cost is linear in the step).  ``large_full=True`` is allowed beside it (objective and rollout);
-        ``large_hessian``, ``large_reduce``, ``exp_hessian`` and ``exp_full`` are not: solve with a quasi-Newton Hessian.  Never set on its own;
-        at a dimension up to 64 the ordinary exponential context serves the constraint as always."""
+        ``large_hessian``, ``large_reduce``, ``exp_hessian`` and ``exp_full`` are not: solve with a quasi-Newton Hessian, or set ``large_exp_hessian`` (below).  Never set on its own;
+        at a dimension up to 64 the ordinary exponential context serves the constraint as always.
+        ``large_exp_hessian=True`` (with ``large_exp=True`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served at
+        those dimensions too (the library's option ``large_exp_hess``: the adjoint of the Jacobian's substepped recurrence with the second
+        derivative carried; values, order and structure are those of ``exp_hessian``) -- ``hessian_structure`` and
+        ``eval_hessian_of_lagrangian`` work.  Off by default and never on by itself; at a dimension up to 64 it sets nothing (``exp_hessian`` is
+        that context's switch)."""
+        _check_large_exp_hessian(large_exp_hessian, large_exp)
         _check_large_exp(large_exp, large_generator, pade_order)
         _check_large_hessian(large_hessian, large_generator, pade_order)
         _check_large_full(large_full, large_generator, pade_order, PCL_BATCH_MEMBERS, large_exp)
@@ -709,7 +739,7 @@ class HipPadeIntegrator:
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
             state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
-            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce, large_exp=large_exp,
+            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
         )  # fmt: skip
         self._large_generator = bool(large_generator)
         self._large_exp = bool(large_exp)
@@ -774,7 +804,8 @@ class HipVariationalIntegrator:
     path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False):
+                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False):
+        _check_large_exp_hessian(large_exp_hessian, large_exp, PCL_BATCH_VARIATIONAL)
         _check_large_exp(large_exp, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
@@ -1124,7 +1155,11 @@ def BilinearIntegrator(system, traj, x_name=None, u_name="u", **kw):
     [REF src/control/templates/sampling_problem.jl:190-223].  Members that share the drive generators (per-member
     ``H_drift`` only -- BASELINE config 4) evaluate through one batched context; an ensemble whose members differ in
     their drive generators too (each member uses its full ``sys.G`` [REF integrators.jl:149-162]) gets one context per
-    member."""
+    member.
+
+    The keywords are ``HipPadeIntegrator``'s.  Among them ``large_generator=True, large_exp=True`` with ``pade_order="exp"`` is the exponential
+    constraint at generator dimensions 66 .. 128 (residual and Jacobian), and ``large_exp_hessian=True`` beside them serves its Hessian of the
+    Lagrangian as well -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work; without ``large_exp=True`` it is a ``ValueError``."""
     if isinstance(system, (list, tuple)):
         from .quantum import OpenQuantumSystem
         from .trajectory import DENSITY

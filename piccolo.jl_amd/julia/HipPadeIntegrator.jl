@@ -86,7 +86,13 @@ end
 function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}, N::Int, z_dim::Int, u_off::Int, dt_off::Int,
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
                       exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
-                      large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false)
+                      large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false,
+                      large_exp_hessian::Bool = false)
+    # large_exp_hessian = true (with large_exp = true only, hence large_generator = true and pade_order = :exp): the library's option large_exp_hess --
+    # the Hessian of the Lagrangian of the exponential constraint at generator dimensions 66 .. 128 (hess_per > 0, eval_hessian = true works).  At
+    # n <= 64 it sets nothing (exp_hessian is that context's switch).  Never set on its own.
+    (large_exp_hessian && !large_exp) &&
+        throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is the Hessian of the Lagrangian of a context created with large_exp = true (large_generator = true, pade_order = :exp): it needs that keyword"))
     # large_exp = true (with large_generator = true and pade_order = :exp only): the library's second flag PCL_LARGE_EXP in batch_mode -- the
     # exponential constraint at generator dimensions 66 .. 128, residual and exact Jacobian (hess_per = 0: solve with eval_hessian = false).
     # large_full = true is allowed beside it; the other large options and the exponential ones are refused by the library.  Never set on its own.
@@ -144,9 +150,11 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     # (exp_full: the library's option of that name -- the host-pointer calls below then move the compact values over PCIe and expand on the host)
     exp_full && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "exp_full", 1))
     (large && large_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_hess", 1))
+    (large && large_exp && large_exp_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_exp_hess", 1))
     (large && large_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_full", 1))
     (large && large_reduce) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_reduce", 1))
-    ((pade_order == PCL_ORDER_EXP && !exp_hessian) || (large && !large_hessian)) ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
+    served = large ? (large_exp ? large_exp_hessian : large_hessian) : (pade_order != PCL_ORDER_EXP || exp_hessian)
+    !served ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     return core, Int(ncol[])
@@ -215,7 +223,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
-const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true
+const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -315,7 +323,9 @@ end
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false)
+                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false,
+                      large_exp_hessian::Bool = false)
+    large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_reduce && throw(ArgumentError("HipPadeIntegrator: large_reduce = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)"))
     large_full && throw(ArgumentError("HipPadeIntegrator: large_full = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)"))
