@@ -285,7 +285,17 @@ typedef enum pcl_status {
  * atomics, every work split, two launches and both pointer paths give the same bits.  Back at 0 the refusals return, in the same words; the
  * compact trio, the merit / reduce entry points and the options "exp_hess", "large_hess" = 1 stay refused at either value.
  * "large_exp_hess_drives" caps the drives per group of that launch (0 auto; PCL_EINVAL when negative or off such a context), "cols_per_slice"
- * its state columns per workgroup; get_option "last_hess_kernel" reads 320 after it. */
+ * its state columns per workgroup; get_option "last_hess_kernel" reads 320 after it.
+ * Option "large_exp_reduce" (default 0, never on by itself; 1 on any other context and any value but 0 and 1: PCL_EINVAL; it reads 0 everywhere
+ * else; independent of "large_full" and "large_exp_hess"): at 1 pcl_jac_compact_nnz, pcl_eval_jac_compact_dev, pcl_jac_expand_dev,
+ * pcl_merit_grad_len, pcl_merit_grad_dev and pcl_eval_jac_merit_dev (vals = NULL accepted: delta and the payload alone) are served with the
+ * contracts of the option "exp_full" at n <= 64 -- compact layout per interval [-E (n^2) | tails x_dim (m + 1)], tails in the order of the full
+ * layout -- as modes of the one kernel, and the host-pointer calls take the compact route where blocks are replicated (cols > 1,
+ * "host_path" != 1).  pcl_eval_jac_merit_objective_dev also needs "large_full" = 1 and a unitary goal; member weights come from pcl_set_weights,
+ * hence "large_full".  The compact trio honours the member window, the merit entry points cover every member.  Compact values = full values,
+ * expansion = pcl_eval_jac_dev, fused payload = payload alone, every work split: the same bits.  Back at 0 the refusals return, in the same
+ * words; "exp_full" and "large_reduce" = 1 stay PCL_ENOTIMPL at either value.  get_option "last_kernel" reads 322 after the compact launch and
+ * 323 after the payload-only launch (320 after the full-values launch with or without the payload's partial sums: "last_merit_fused" tells). */
 #define PCL_LARGE_EXP 0x200
 
 typedef struct pcl_desc {

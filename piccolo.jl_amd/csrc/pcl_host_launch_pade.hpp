@@ -263,11 +263,14 @@ static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac, int mode =
 // the fewest units that fit and the fewest whose columns of E end with the chain's last 16-column tile, the plan with the shortest launch is
 // taken: ceil(W / 16) tile passes per unit times the rounds of the grid over the CUs; on a tie the fewest passes in all, then the larger
 // group.  Option general_slices: that many units at least.  Every split gives the same bits.
+// The payload-only launch (option large_exp_reduce, pcl_eval_jac_merit_dev without values; mode LE_PAYLOAD): the slices of the Jacobian plan, chain
+// units alone -- no column of E, so a group may fill a buffer: nc (1 + mg) <= NBW (option large_exp_drives caps mg) -- chosen by the same count
+// (tile passes times rounds of the grid, then the fewest passes, then the larger group); U = sx ngrp, npc = 0, LDS = fixed + 3 LD nc (1 + mg).
 struct LargeExpPlan {
     int LD, threads, NB, NBW, sx, nc, mg, ngrp, U, npc, W;
     size_t lds;
 };
-static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargeExpPlan &P) {
+static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargeExpPlan &P, bool payload_only = false) {
     P.LD = n | 1;
     P.threads = 64 * ((n + 15) / 16);
     const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
@@ -279,7 +282,19 @@ static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac,
     P.sx = (cols + P.nc - 1) / P.nc;
     P.nc = (cols + P.sx - 1) / P.sx;  // even slices
     P.mg = 0, P.ngrp = 1, P.U = P.sx, P.npc = 0;
-    if (jac) {
+    if (jac && payload_only) {
+        int mg_fit = drv ? std::max(1, std::min(m, P.NBW / P.nc - 1)) : 0;
+        if (drv && ctx->opt_large_exp_drives > 0) mg_fit = (int)std::min<int64_t>(mg_fit, ctx->opt_large_exp_drives);
+        long long best_t = -1, best_p = -1;
+        for (int mg0 = mg_fit; mg0 >= (drv ? 1 : 0); --mg0) {
+            const int ngrp = drv ? (m + mg0 - 1) / mg0 : 1, mg = drv ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            const int U = P.sx * ngrp;
+            const long long tiles = (P.nc * (1 + mg) + 15) / 16, rounds = (std::max(items, 1LL) * U + ctx->n_cu - 1) / std::max(ctx->n_cu, 1);
+            const long long t = tiles * rounds, passes = tiles * U;
+            if (best_t < 0 || t < best_t || (t == best_t && passes < best_p)) best_t = t, best_p = passes, P.mg = mg, P.ngrp = ngrp, P.U = U;
+            if (!drv) break;
+        }
+    } else if (jac) {
         int mg_fit = drv ? std::max(1, std::min(m, (P.NBW - 1) / P.nc - 1)) : 0;
         if (drv && ctx->opt_large_exp_drives > 0) mg_fit = (int)std::min<int64_t>(mg_fit, ctx->opt_large_exp_drives);
         // per group size two candidates: the fewest units that fit, and the fewest whose columns of E end with the chain's last column tile
@@ -304,10 +319,11 @@ static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac,
     P.W = P.nc * (1 + P.mg) + P.npc;
     P.lds = (size_t)(fixed + 3LL * P.LD * P.W) * sizeof(double);
 }
-static int launch_large_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
+// mode (option large_exp_reduce): LE_FULL | LE_COMPACT | LE_MERIT (p.mpart, p.mlam set) | LE_PAYLOAD (the same, no values) -- pcl_kernel_large_exp.hpp
+static int launch_large_exp(pcl_ctx *ctx, KParams &p, bool want_jac, int mode = LE_FULL) {
     LargeExpPlan P;
     const long long items = (long long)p.batch * p.K;
-    large_exp_plan(ctx, p.n, p.cols, p.m, want_jac, items, P);
+    large_exp_plan(ctx, p.n, p.cols, p.m, want_jac, items, P, mode == LE_PAYLOAD);
     if (P.lds > (size_t)ctx->max_lds)
         return fail(ctx, PCL_ESHAPE, "the large exponential kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, p.n, p.m);
     p.LD = P.LD;
@@ -318,11 +334,16 @@ static int launch_large_exp(pcl_ctx *ctx, KParams &p, bool want_jac) {
     const long long grid = items * P.U;
     if (int rc = check_grid(ctx, grid)) return rc;
     typedef void (*kern_t)(const KParams, const int, const int, const int);
-    const kern_t kern = want_jac ? (kern_t)pcl_large_exp_kernel<true> : (kern_t)pcl_large_exp_kernel<false>;
+    const kern_t kern = !want_jac            ? (kern_t)pcl_large_exp_kernel<false>
+                        : mode == LE_COMPACT ? (kern_t)pcl_large_exp_kernel<true, LE_COMPACT>
+                        : mode == LE_MERIT   ? (kern_t)pcl_large_exp_kernel<true, LE_MERIT>
+                        : mode == LE_PAYLOAD ? (kern_t)pcl_large_exp_kernel<true, LE_PAYLOAD>
+                                             : (kern_t)pcl_large_exp_kernel<true>;
     if (int rc = set_lds_attr(ctx, (const void *)kern, want_jac ? 7 : 8, P.lds)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, P.sx, P.mg, P.npc);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->last_kernel = want_jac ? 320 : 321;  // the large exponential kernel: residual + Jacobian | residual only
+    // the large exponential kernel: 320 residual + Jacobian (with or without the payload's partial sums) | 321 residual only | 322 the compact values | 323 the payload alone
+    ctx->last_kernel = !want_jac ? 321 : mode == LE_COMPACT ? 322 : mode == LE_PAYLOAD ? 323 : 320;
     ctx->last_n_stream = 0;
     return PCL_OK;
 }
@@ -878,7 +899,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
         return var_launch_fused(ctx, Z, delta, jac, compact && jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
-    if (ctx->exp && compact && !ctx->exp_full) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
+    if (ctx->exp && compact && !ctx->exp_full && !ctx->large_exp_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
     KParams p;
     fill_params(ctx, p);
     p.Z = window_Z(ctx, Z);
@@ -887,8 +908,17 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
-    if (ctx->large_exp) {  // (the compact Jacobian is refused at the entry points: LARGE_NOTIMPL)
-        if (compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP)");
+    if (ctx->large_exp) {  // (without the option large_exp_reduce the compact Jacobian is refused at the entry points: LARGE_NOTIMPL)
+        if (compact && !ctx->large_exp_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP)");
+        if (want_jac && compact) return launch_large_exp(ctx, p, true, LE_COMPACT);
+        // the payload-fused call (pcl_eval_jac_merit_dev, option large_exp_reduce): every member, so that the partial sums are numbered as the finish kernel reads them
+        if (want_jac && ctx->large_exp_reduce && merit_call(ctx, p)) {
+            if (!ctx->dmcols) HIP_TRY(ctx, hipMalloc((void **)&ctx->dmcols, (size_t)ctx->desc.batch * p.K * p.cols * (p.m + 2) * sizeof(double)));
+            p.mpart = ctx->dmcols;
+            p.mlam = ctx->merit_lam;
+            ctx->merit_fused = 1;
+            return launch_large_exp(ctx, p, true, LE_MERIT);
+        }
         return launch_large_exp(ctx, p, want_jac);
     }
     if (ctx->large) {

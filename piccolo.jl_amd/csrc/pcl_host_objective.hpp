@@ -450,6 +450,26 @@ static int launch_large_payload(pcl_ctx *ctx, const double *Z, const double *lam
     TRY(launch_pade_large(ctx, p, true, PL_PAYLOAD));
     return launch_merit_finish(ctx, out);
 }
+// The same for a large exponential context (option large_exp_reduce; mode LE_PAYLOAD of pcl_kernel_large_exp.hpp).  Every member, whatever the window says.
+static int launch_large_exp_payload(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *out) {
+    ON_DEVICE(ctx);
+    if (int rc = check_device_error(ctx, "pcl_eval_jac_merit_dev")) return rc;
+    const pcl_desc &D = ctx->desc;
+    const int wf = ctx->win_first, wc = ctx->win_count;
+    ctx->win_first = 0, ctx->win_count = D.batch;
+    KParams p;
+    fill_params(ctx, p);
+    ctx->win_first = wf, ctx->win_count = wc;
+    p.Z = Z;
+    p.delta = delta;
+    p.jac = nullptr;
+    p.jac_per = 0;
+    if (!ctx->dmcols) HIP_TRY(ctx, hipMalloc((void **)&ctx->dmcols, (size_t)D.batch * p.K * p.cols * (p.m + 2) * sizeof(double)));
+    p.mpart = ctx->dmcols;
+    p.mlam = lam;
+    TRY(launch_large_exp(ctx, p, true, LE_PAYLOAD));
+    return launch_merit_finish(ctx, out);
+}
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
     LARGE_REDUCE_GATE(ctx, "pcl_merit_grad_dev");
@@ -472,9 +492,9 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
     LARGE_REDUCE_GATE(ctx, "pcl_eval_jac_merit_dev");
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
-    if (ctx && ctx->large && Z && delta && out && !vals) {  // the payload alone: no Jacobian value is formed (vals may be NULL under large_reduce)
+    if (ctx && ctx->large && Z && delta && out && !vals) {  // the payload alone: no Jacobian value is formed (vals may be NULL under large_reduce / large_exp_reduce)
         ctx->merit_fused = 0;
-        return launch_large_payload(ctx, Z, lam, delta, out);
+        return ctx->large_exp ? launch_large_exp_payload(ctx, Z, lam, delta, out) : launch_large_payload(ctx, Z, lam, delta, out);
     }
     if (ctx && ctx->exp && !ctx->exp_full && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_dev");
@@ -493,7 +513,7 @@ extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const doubl
     if (rc != PCL_OK) return rc;
     if (!ctx->merit_fused) return pcl_merit_grad_dev(ctx, delta, lam, vals, out);  // other kernels / member windows: the separate payload kernels
     ON_DEVICE(ctx);
-    if (ctx->exp) return merit_sum(ctx, out);  // (the exponential kernel left the sums per (member, interval): nothing to add over columns)
+    if (ctx->exp && !ctx->large_exp) return merit_sum(ctx, out);  // (the exponential kernel left the sums per (member, interval): nothing to add over columns)
     return launch_merit_finish(ctx, out);
 }
 // the payload from the partial sums per state column in ctx->dmcols (the fused kernels leave them): ONE launch
@@ -754,7 +774,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 // regulariser rows, the terminal infidelities and the payload's finish (pcl_ens_tail_kernel); the same bits as the separate calls.
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
-    if (ctx && !(ctx->large_reduce && ctx->large_full)) LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");  // (a large context: both options)
+    if (ctx && !((ctx->large_reduce || ctx->large_exp_reduce) && ctx->large_full)) LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");  // (a large context: both options)
     VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
     EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_objective_dev");
     if (!ctx) return PCL_EINVAL;

@@ -78,6 +78,11 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
         if (v < 0 || !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_hess_drives must be >= 0, on a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension above 64)");
         ctx->opt_large_exp_hess_drives = v;
     }
+    else if (!strcmp(key, "large_exp_reduce")) {  // large exponential contexts: serve the compact Jacobian trio, the host calls' compact route and the merit / reduce payload (0: refuse them, the default)
+        if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "large_exp_reduce must be 0 or 1");
+        if (v && !ctx->large_exp) return fail(ctx, PCL_EINVAL, "large_exp_reduce = 1 needs a large exponential context (batch_mode | PCL_LARGE_N | PCL_LARGE_EXP, pade_order = PCL_ORDER_EXP, at a generator dimension above 64); every other context serves its compact Jacobian and reduce payload without it or by an option of its own");
+        ctx->large_exp_reduce = (int)v;
+    }
     else if (!strcmp(key, "large_full")) {  // large contexts: serve the objective family and the rollout (0: refuse them, the default, and drop goal, weights, regularisers)
         TRY(large_set_full(ctx, v));
     }
@@ -249,6 +254,8 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->large_exp_hess;
     else if (!strcmp(key, "large_exp_hess_drives"))
         *v = ctx->opt_large_exp_hess_drives;
+    else if (!strcmp(key, "large_exp_reduce"))
+        *v = ctx->large_exp_reduce;
     else if (!strcmp(key, "large_full"))
         *v = ctx->large_full;
     else if (!strcmp(key, "large_reduce"))

@@ -32,13 +32,27 @@
 // Every element of every output is formed by one fixed sequence of operations whatever the split (sx, mg, npc): the k order of the products is
 // pl_tile's, the additive terms are explicit fused multiply-adds -- no atomics, and every split gives the same bits; the residual-only launch
 // runs V alone and gives the bits of the fused launch.  Odd n (PCL_STATE_VECTOR): the blocks are not 16-byte aligned; the stores are scalar.
+//
+// MODE (option large_exp_reduce; the plain launch is LE_FULL, the code it had before the modes -- they mirror pcl_kernel_pade_large.hpp):
+//   LE_COMPACT  the compact Jacobian [-E (n n) | tails]: every unit stores its panel once instead of `cols` times, the ones of d delta / d X_{k+1}
+//               are not written and the tails start behind n n; the same registers and operations, so the values and delta have the same bits;
+//   LE_MERIT    the full values and, behind the last substep and the G Y product, the reduce payload's partial sums: a chain unit (slice s, group g)
+//               forms, per state column of its slice, <d delta / d u_l, lam> for each of its drives (-dY_l in LDS), and group 0 also
+//               <d delta / d dt, lam> (-G Y) and <lam, delta> (times 1/2 when lam = delta; delta is then staged in the free buffer) -- one wave per
+//               (column, job), lane i takes rows i and i + 64 by fused multiply-adds in that order, then the shuffle tree: the order of the additions
+//               depends on n alone.  Plain stores into p.mpart[((b K + k) cols + c)(m + 2) + l], which pcl_merit_finish_kernel reads; exactly one
+//               unit owns each (c, l), panel-only units own nothing: no atomics, no sum across units, every split the same bits;
+//   LE_PAYLOAD  delta and those partial sums alone (npc = 0, U = sx ngrp chain units): no identity panel, no block store, no tail store.
 #pragma once
 
 #define LE_DEG 18  // (the builder's choice; LR_DEG of the rollout, whose discretisation the rows then share)
 
 // p.S = U units per interval, p.nc state columns per chain unit; sx state-column slices, mg drives per group, npc columns of E per unit
-template <bool JAC>
+enum { LE_FULL = 0, LE_COMPACT = 1, LE_MERIT = 2, LE_PAYLOAD = 3 };
+template <bool JAC, int MODE = LE_FULL>
 __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, const int sx, const int mg, const int npc) {
+    static_assert(JAC || MODE == LE_FULL, "the modes belong to the Jacobian launch");
+    constexpr bool PANEL = JAC && MODE != LE_PAYLOAD;  // the panel of the identity: the columns of E
     extern __shared__ double lds[];
     const int n = p.n, d = p.cols, m = p.m, LD = p.LD, nc = p.nc, U = p.S;
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, rt = tid >> 6;  // one wave per row tile
@@ -57,8 +71,8 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
     const int c0 = s * nc, nce = chain ? max(0, min(nc, d - c0)) : 0;           // this unit's state columns
     const int l0 = g * mg, mge = (JAC && chain) ? max(0, min(mg, m - l0)) : 0;  // ... and drives
     const int T = JAC ? 1 + mg : 1;                                             // blocks per state column: V | dV_l0 ..
-    const int W = T * nc + (JAC ? npc : 0), cx = chain ? T * nc : 0;            // columns of a buffer; the chain's share of them
-    const int pc0 = JAC ? u * npc : n, npce = max(0, min(npc, n - pc0));        // ... and columns of E
+    const int W = T * nc + (PANEL ? npc : 0), cx = chain ? T * nc : 0;          // columns of a buffer; the chain's share of them
+    const int pc0 = PANEL ? u * npc : n, npce = max(0, min(npc, n - pc0));        // ... and columns of E
     double *G = lds, *B0 = G + LD * n, *B1 = B0 + LD * W, *B2 = B1 + LD * W;
     double *us = B2 + LD * W + PL_SLACK;
     for (int e = tid; e < p.lds_doubles; e += nth) lds[e] = 0.0;
@@ -162,13 +176,44 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
             p.delta[item * xd + (long long)c0 * n + e] = zn[x_off + (c0 + c) * n + i] - Y[i + LD * c];
         }
     if (!JAC) return;
+    const int nl = mge + (first ? 1 : 0);
+    if (MODE == LE_MERIT || MODE == LE_PAYLOAD) {
+        // the payload's partial sums of this unit's columns: jobs t < mge its drives, then (group 0) dt and <lam, delta>; lam = delta is staged in the
+        // free buffer by the expression of the store above
+        const double *lamg = p.mlam ? p.mlam + item * xd + (long long)c0 * n : nullptr;
+        if (!lamg) {
+            for (int e = tid; e < nce * n; e += nth) {
+                const int c = e / n, i = e - c * n;
+                f2[i + LD * c] = zn[x_off + (c0 + c) * n + i] - Y[i + LD * c];
+            }
+            __syncthreads();
+        }
+        const int nj = nl + (first ? 1 : 0), nw = nth >> 6;
+        for (int job = rt; job < nce * nj; job += nw) {
+            const int c = job / nj, t = job - c * nj;
+            const double *x = t < mge ? Y + LD * ((1 + t) * nc + c) : f1 + LD * c;  // dY_l | G Y: the tails are their negatives
+            const double *lm = lamg ? lamg + c * n : f2 + LD * c;
+            double sacc = 0.0;
+            if (t <= mge) {
+                for (int i = lane; i < n; i += 64) sacc = __builtin_fma(-x[i], lm[i], sacc);
+            } else if (lamg) {
+                for (int i = lane; i < n; i += 64) sacc = __builtin_fma(zn[x_off + (c0 + c) * n + i] - Y[i + LD * c], lm[i], sacc);
+            } else {
+                for (int i = lane; i < n; i += 64) sacc = __builtin_fma(lm[i], lm[i], sacc);
+            }
+            for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
+            if (t == mge + 1 && !lamg) sacc *= 0.5;
+            if (lane == 0) p.mpart[(item * d + c0 + c) * (m + 2) + (t < mge ? l0 + t : m + (t - mge))] = sacc;
+        }
+        if (MODE == LE_PAYLOAD) return;
+    }
     double *jb = p.jac + item * p.jac_per;
-    // d delta / d X_{k+1} = I: its diagonal, from the unit that has the column
-    if (first)
+    const int dcp = MODE == LE_COMPACT ? 1 : d;  // copies of -E in the layout
+    // d delta / d X_{k+1} = I: its diagonal, from the unit that has the column (not part of the compact layout)
+    if (MODE != LE_COMPACT && first)
         for (int e = tid; e < nce * n; e += nth) jb[d * nn + (long long)c0 * n + e] = 1.0;
     // tails [c][l | dt][i]: this group's drives, and the dt block from group 0
-    double *jt = jb + d * nn + xd;
-    const int nl = mge + (first ? 1 : 0);
+    double *jt = jb + dcp * nn + (MODE == LE_COMPACT ? 0 : xd);
     for (int e = tid; e < nl * nce * n; e += nth) {
         const int i = e % n, t = (e / n) % nl, c = e / (n * nl);
         const int l = t < mge ? l0 + t : m;
@@ -184,12 +229,12 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
             for (int e = tid; e < npce * hn; e += nth) {
                 const int c = e / hn, i = 2 * (e - c * hn);
                 const double v0 = -src[i + LD * c], v1 = -src[i + 1 + LD * c];
-                for (int cc = 0; cc < d; ++cc) store2(o0 + cc * nn + c * n + i, v0, v1, p.nt);
+                for (int cc = 0; cc < dcp; ++cc) store2(o0 + cc * nn + c * n + i, v0, v1, p.nt);
             }
         } else {
             for (int e = tid; e < npce * n; e += nth) {
                 const double v = -src[(e % n) + LD * (e / n)];
-                for (int cc = 0; cc < d; ++cc) o0[cc * nn + e] = v;
+                for (int cc = 0; cc < dcp; ++cc) o0[cc * nn + e] = v;
             }
         }
     }

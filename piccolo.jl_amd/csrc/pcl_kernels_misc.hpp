@@ -152,6 +152,76 @@ __global__ __launch_bounds__(256) void pcl_exp_expand_kernel(const double *__res
     }
 }
 
+// The same for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, option large_exp_reduce): a tile has up to 8192 element pairs (n = 128), so
+// a slice of cpi state columns is split over P = pcl_expand_large_parts(n) workgroups of 2048 pairs (4096 doubles) each; the rule stays: request
+// everything, then only issue the stores of the slice's copies (nt: nontemporal).  16-byte accesses where n is even and both arrays are 16-byte
+// aligned; scalar otherwise (PCL_STATE_VECTOR with an odd n: sixteen doubles per thread and part) -- at one column too, since
+// the full layout has the ones between the tile and the tails.  Tail workgroups as in pcl_exp_expand_kernel; the first also writes the ones.
+//   per interval: S P block workgroups in address order (slice, part), then T tail workgroups.  Copies only: the bits of the compact values.
+__global__ __launch_bounds__(256) void pcl_exp_expand_large_kernel(const double *__restrict__ compact, double *__restrict__ full, int cols, int n, int m,
+                                                                   long long n_bk, int cpi, int nt) {
+    const long long nn = (long long)n * n, xd = (long long)n * cols, tail = xd * (m + 1);
+    const long long cper = nn + tail, fper = cols * nn + xd + tail;
+    const int S = (cols + cpi - 1) / cpi, T = (int)((tail + 4095) / 4096);
+    const bool pairs = !(n & 1) && !((reinterpret_cast<unsigned long long>(compact) | reinterpret_cast<unsigned long long>(full)) & 15ull);
+    const int PG = pcl_expand_large_parts(n);  // (an odd n <= 128: n n - 1 is no multiple of 4096, so these parts of 4096 doubles cover the tile)
+    const int per_bk = S * PG + T;
+    const long long bk = blockIdx.x / per_bk;
+    const int r = (int)(blockIdx.x - bk * per_bk);
+    if (bk >= n_bk) return;
+    const double *src = compact + bk * cper;
+    double *dst = full + bk * fper;
+    const int tid = threadIdx.x;
+    if (r < S * PG) {
+        const int sl = r / PG, part = r - sl * PG;
+        const int c0 = sl * cpi, c1 = min(cols, c0 + cpi);
+        if (pairs) {
+            const int nn2 = (int)(nn >> 1), e0 = part * 2048;  // this workgroup's pairs [e0, e0 + 2048) of the tile
+            double2_t v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (e0 + tid + 256 * q < nn2) v[q] = *reinterpret_cast<const double2_t *>(src + 2 * (e0 + tid + 256 * q));
+            double *o = dst + (long long)c0 * nn;
+            for (int c = c0; c < c1; ++c, o += nn) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    if (e0 + tid + 256 * q < nn2) store2(o + 2 * (e0 + tid + 256 * q), v[q][0], v[q][1], nt);
+            }
+        } else {
+            const int e0 = part * 4096;  // this workgroup's doubles [e0, e0 + 4096) of the tile
+            double v[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                if (e0 + tid + 256 * q < nn) v[q] = src[e0 + tid + 256 * q];
+            double *o = dst + (long long)c0 * nn;
+            for (int c = c0; c < c1; ++c, o += nn) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if (e0 + tid + 256 * q < nn) {
+                        if (nt)
+                            __builtin_nontemporal_store(v[q], o + e0 + tid + 256 * q);
+                        else
+                            o[e0 + tid + 256 * q] = v[q];
+                    }
+            }
+        }
+    } else {
+        const long long e0 = (long long)(r - S * PG) * 4096, e1 = min(tail, e0 + 4096);
+        src += nn;
+        double *ones = dst + cols * nn;
+        dst = ones + xd;
+        if (pairs) {
+            for (long long e = e0 + 2 * tid; e < e1; e += 512) *reinterpret_cast<double2_t *>(dst + e) = *reinterpret_cast<const double2_t *>(src + e);
+            if (r == S * PG)
+                for (long long e = 2 * tid; e < xd; e += 512) *reinterpret_cast<double2_t *>(ones + e) = double2_t{1.0, 1.0};
+        } else {
+            for (long long e = e0 + tid; e < e1; e += 256) dst[e] = src[e];
+            if (r == S * PG)
+                for (long long e = tid; e < xd; e += 256) ones[e] = 1.0;
+        }
+    }
+}
+
 // The same for a variational context (option var_compact), either constraint kind; xd = (1 + v) n cols is the stacked state, tail = xd (m + 1):
 //   Pade         compact [-B+ | B- | per variation i: -L+_i | L-_i | tail] -> full [-B+ x cols | B- x cols | per i: -B+ x cols | B- x cols | -L+_i x cols | L-_i x cols | tail]
 //   exponential  compact [-E | -L_1 .. -L_v | tail]                        -> full [-E x cols | per i: -E x cols | -L_i x cols | ones (xd) | tail]

@@ -85,10 +85,11 @@ struct pcl_ctx {
     int large_reduce = 0;                  // ... option large_reduce: the compact Jacobian trio, the host calls' compact route and the merit / reduce payload are served (the modes of pcl_kernel_pade_large.hpp, pcl_expand_large_kernel)
     int64_t opt_large_rollout_stage = 0;   // ... ... measurements: 0 both launches of the rollout | 1 the propagators only | 2 the chain only, on the workspace as it stands
     double *dlhpart = nullptr;             // ... ... its workspace: per (member, interval, state column) the m (m + 1) + 1 partial sums (allocated when the option is first set to 1)
-    int large_exp = 0;                     // ... PCL_LARGE_EXP with PCL_ORDER_EXP (then `large` and `exp` are set too): every residual / Jacobian launch is pcl_large_exp_kernel (pcl_kernel_large_exp.hpp); large_full serves the objective and the rollout, everything else is refused
+    int large_exp = 0;                     // ... PCL_LARGE_EXP with PCL_ORDER_EXP (then `large` and `exp` are set too): every residual / Jacobian launch is pcl_large_exp_kernel (pcl_kernel_large_exp.hpp); large_full serves the objective and the rollout, the two options below the Hessian of the Lagrangian and the compact Jacobian / reduce payload, everything else is refused
     int64_t opt_large_exp_drives = 0;      // ... ... the most drives per group of that launch (0 auto)
     int large_exp_hess = 0;                // ... ... option large_exp_hess: its Hessian of the Lagrangian is served (pcl_kernel_large_exp_hess.hpp)
     int64_t opt_large_exp_hess_drives = 0; // ... ... ... the most drives per group of that launch (0 auto: as many as fit)
+    int large_exp_reduce = 0;              // ... ... option large_exp_reduce: the compact Jacobian trio, the host calls' compact route and the merit / reduce payload are served (the modes of pcl_kernel_large_exp.hpp, pcl_exp_expand_large_kernel)
     double *dlehpart = nullptr;            // ... ... ... its workspace: per (member, interval, state column) the (m + 1)(m + 2) / 2 partial sums (allocated when the option is first set to 1)
     int exp = 0;  // PCL_ORDER_EXP: delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (pcl_kernel_exp.hpp); no order; the Hessian, the compact Jacobian and the payload by option
     int exp_hess = 0;            // ... option exp_hess: the Hessian of the Lagrangian is served (pcl_kernel_exp_hess.hpp)
@@ -429,20 +430,21 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
         if ((ctx) && !(ctx)->large_full) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
-// ... and the compact Jacobian trio and the merit / reduce entry points by option large_reduce only: without it, the same words
+// ... and the compact Jacobian trio and the merit / reduce entry points by option large_reduce only (a large exponential context: by option
+// large_exp_reduce): without it, the same words
 #define LARGE_REDUCE_GATE(ctx, what)                                \
     do {                                                            \
-        if ((ctx) && !(ctx)->large_reduce) LARGE_NOTIMPL(ctx, what); \
+        if ((ctx) && !(ctx)->large_reduce && !(ctx)->large_exp_reduce) LARGE_NOTIMPL(ctx, what); \
     } while (0)
 
 #define EXP_HESS_GATE(ctx, what)                       \
     do {                                               \
         if ((ctx) && !(ctx)->exp_hess && !(ctx)->large_exp_hess) EXP_NOTIMPL(ctx, what); \
     } while (0)
-// ... and the compact Jacobian trio and the merit / reduce entry points unless its option exp_full is on
+// ... and the compact Jacobian trio and the merit / reduce entry points unless its option exp_full is on (a large exponential context: large_exp_reduce)
 #define EXP_FULL_GATE(ctx, what)                       \
     do {                                               \
-        if ((ctx) && !(ctx)->exp_full) EXP_NOTIMPL(ctx, what); \
+        if ((ctx) && !(ctx)->exp_full && !(ctx)->large_exp_reduce) EXP_NOTIMPL(ctx, what); \
     } while (0)
 
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
@@ -1242,6 +1244,14 @@ extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *v
     if (ctx->exp) {  // [-E | tail] -> [-E x cols | ones | tail], at every column count (one column: the ones are not part of the compact block)
         const int cpi = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->opt_cols_per_slice > 0 ? ctx->opt_cols_per_slice : 3, ctx->cols));
         const long long tail = (long long)ctx->x_dim * (ctx->desc.n_drives + 1);
+        if (ctx->large_exp) {  // tiles of up to 8192 element pairs (option large_exp_reduce): workgroups of 2048 pairs each per slice -- pcl_exp_expand_large_kernel
+            const long long grid_l = n_bk * ((long long)pcl_expand_large_parts(ctx->n) * ((ctx->cols + cpi - 1) / cpi) + (tail + 4095) / 4096);
+            if (grid_l > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid_l);
+            hipLaunchKernelGGL(pcl_exp_expand_large_kernel, dim3((unsigned)grid_l), dim3(256), 0, ctx->stream, compact, vals, ctx->cols, ctx->n, ctx->desc.n_drives, n_bk, cpi,
+                               (int)(ctx->opt_nt > 0 ? ctx->opt_nt : 0));
+            HIP_TRY(ctx, hipGetLastError());
+            return PCL_OK;
+        }
         const long long grid = n_bk * ((ctx->cols + cpi - 1) / cpi + (tail + 4095) / 4096);
         if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_jac_expand_dev: %lld work items exceed the grid limit", grid);
         hipLaunchKernelGGL(pcl_exp_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, compact, vals, ctx->cols, ctx->n, ctx->desc.n_drives, n_bk, cpi);
@@ -1431,8 +1441,9 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
     // (variational contexts without the option var_compact, and exponential ones without the option exp_full: full values, host_path 1)
-    // (large contexts: by the option large_reduce)
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->large || ctx->large_reduce) && (!ctx->var || ctx->var_compact) && (!ctx->exp || ctx->exp_full);
+    // (large contexts: by the option large_reduce; large exponential ones: by the option large_exp_reduce)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->large || ctx->large_reduce || ctx->large_exp_reduce) && (!ctx->var || ctx->var_compact) &&
+                              (!ctx->exp || ctx->exp_full || ctx->large_exp_reduce);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));

@@ -146,13 +146,28 @@ def _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode=PCL_BATCH_
                          "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
 
 
+def _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_exp_reduce`` (the library's option of that name: the compact Jacobian, the host-pointer calls' compact route and the
+    merit / reduce payload of the exponential constraint at generator dimensions 66 .. 128) goes with ``large_exp=True`` -- and hence
+    ``large_generator=True`` and ``pade_order="exp"`` -- on a plain context: anything else is a ``ValueError``, before any device call."""
+    if not large_exp_reduce:
+        return
+    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
+        raise ValueError("large_exp_reduce=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)")
+    if not large_exp:
+        raise ValueError("large_exp_reduce=True is the compact Jacobian and the reduce payload of a context created with large_exp=True "
+                         "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
-                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False):  # fmt: skip
+                 large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
+                 large_exp_reduce=False):  # fmt: skip
         _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode)
+        _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode)
         _check_large_exp(large_exp, large_generator, pade_order, batch_mode)
         _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
         _check_large_full(large_full, large_generator, pade_order, batch_mode, large_exp)
@@ -211,9 +226,11 @@ class _PclContext:
         # flag changes nothing.  ``large_hessian`` switches the library's option large_hess on there: hess_nnz / hess_per follow it (set_option)
         self.large = bool(large_generator) and n > 64
         # ``large_exp`` (the flag PCL_LARGE_EXP beside it, pade_order "exp"): residual and Jacobian of the exponential constraint there, the
-        # objective and the rollout by ``large_full``; the Hessian of the Lagrangian, the compact Jacobian and the payload raise
+        # objective and the rollout by ``large_full``; the Hessian of the Lagrangian (unless ``large_exp_hessian``), the compact Jacobian and the
+        # payload (unless ``large_exp_reduce``) raise
         self.large_exp = bool(large_exp) and self.large
         self.large_exp_hessian = False  # (``large_exp_hessian`` switches the library's option large_exp_hess on there: hess_nnz / hess_per follow it, set_option)
+        self.large_exp_reduce = False  # (``large_exp_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
         self.large_hessian = False
         self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
         self.large_reduce = False  # (``large_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
@@ -236,6 +253,8 @@ class _PclContext:
             self.set_option("large_full", 1)
         if large_reduce and self.large:  # (at n <= 64 the ordinary context serves them as always: the option is not set)
             self.set_option("large_reduce", 1)
+        if large_exp_reduce and self.large_exp:  # (at n <= 64 ``exp_full`` is the ordinary exponential context's switch: the option is not set)
+            self.set_option("large_exp_reduce", 1)
         if var_compact:
             self.set_option("var_compact", 1)
         # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
@@ -394,7 +413,7 @@ class _PclContext:
             if self.large_hessian or self.large_exp_hessian:
                 self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
                 self.hess_nnz = a.value
-            if self.large_reduce:
+            if self.large_reduce or self.large_exp_reduce:
                 self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
                 self.compact_nnz = a.value
             return
@@ -579,10 +598,16 @@ class _PclContext:
             self.hess_nnz, self.hess_per = a.value, b.value
         if self.large and key == "large_full":
             self.large_full = bool(value)
-        if self.large and key == "large_reduce":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
+        if self.large and not self.large_exp and key == "large_reduce":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
             self.large_reduce = bool(value)
             a, b = ctypes.c_int64(), ctypes.c_int64()
             if self.large_reduce:
+                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
+            self.compact_nnz, self.compact_per = a.value, b.value
+        if self.large_exp and key == "large_exp_reduce":  # ... and on a large exponential context
+            self.large_exp_reduce = bool(value)
+            a, b = ctypes.c_int64(), ctypes.c_int64()
+            if self.large_exp_reduce:
                 self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.compact_nnz, self.compact_per = a.value, b.value
         if key == "var_compact" and self.batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):  # ... the stacked state's compact Jacobian
@@ -591,7 +616,7 @@ class _PclContext:
             if self.var_compact:
                 self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
             self.compact_nnz, self.compact_per = a.value, b.value
-        if self.exponential and key == "exp_full":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
+        if self.exponential and not self.large_exp and key == "exp_full":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
             self.exp_full = bool(value)
             a, b = ctypes.c_int64(), ctypes.c_int64()
             if self.exp_full:
@@ -654,7 +679,7 @@ class HipPadeIntegrator:
 
     def __init__(self, G_drift, G_drives, traj, x_name=STATE, u_name="u", *, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  exp_full=False, var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
-                 large_exp_hessian=False):
+                 large_exp_hessian=False, large_exp_reduce=False):
         """``pade_order=0`` (the default): the smallest diagonal Pade order whose deviation from the reference's exp constraint
         [REF docs/src/concepts/index.md:21] stays below ``order_tol`` over the trajectory's bounds on ``u`` and the timestep
         (``traj.bounds``); without bounds, over ``traj`` itself (x 1.5).  Decided HERE, so every entry point -- host or device
@@ -690,8 +715,13 @@ class HipPadeIntegrator:
         those dimensions too (the library's option ``large_exp_hess``: the adjoint of the Jacobian's substepped recurrence with the second
         derivative carried; values, order and structure are those of ``exp_hessian``) -- ``hessian_structure`` and
         ``eval_hessian_of_lagrangian`` work.  Off by default and never on by itself; at a dimension up to 64 it sets nothing (``exp_hessian`` is
-        that context's switch)."""
+        that context's switch).
+        ``large_exp_reduce=True`` (with ``large_exp=True`` only, else ``ValueError``): the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``,
+        ``eval_jac_compact_dev``, ``jac_expand_dev``, layout ``[-E | tails]`` per interval), the host-pointer calls' compact route and the merit /
+        reduce payload (``merit_grad_len``, ``merit_grad_dev``, ``eval_jac_merit_dev``, also with ``vals=None``) are served there too (the library's
+        option ``large_exp_reduce``).  Off by default and never on by itself; at a dimension up to 64 it sets nothing (``exp_full`` is that context's switch)."""
         _check_large_exp_hessian(large_exp_hessian, large_exp)
+        _check_large_exp_reduce(large_exp_reduce, large_exp)
         _check_large_exp(large_exp, large_generator, pade_order)
         _check_large_hessian(large_hessian, large_generator, pade_order)
         _check_large_full(large_full, large_generator, pade_order, PCL_BATCH_MEMBERS, large_exp)
@@ -739,7 +769,7 @@ class HipPadeIntegrator:
             G0=G_drift, Gj=self.G_drives, batch=len(x_names), batch_mode=PCL_BATCH_MEMBERS, per_member_G0=per_member,
             global_dim=traj.global_dim, device=device, index_base=index_base, pade_order=pade_order,
             state_cols=_lib.PCL_STATE_VECTOR if vec else cols, exp_hessian=exp_hessian, exp_full=exp_full, large_generator=large_generator,
-            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
+            large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce,
         )  # fmt: skip
         self._large_generator = bool(large_generator)
         self._large_exp = bool(large_exp)
@@ -804,8 +834,10 @@ class HipVariationalIntegrator:
     path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False):
+                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
+                 large_exp_reduce=False):
         _check_large_exp_hessian(large_exp_hessian, large_exp, PCL_BATCH_VARIATIONAL)
+        _check_large_exp_reduce(large_exp_reduce, large_exp, PCL_BATCH_VARIATIONAL)
         _check_large_exp(large_exp, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
@@ -1159,7 +1191,8 @@ def BilinearIntegrator(system, traj, x_name=None, u_name="u", **kw):
 
     The keywords are ``HipPadeIntegrator``'s.  Among them ``large_generator=True, large_exp=True`` with ``pade_order="exp"`` is the exponential
     constraint at generator dimensions 66 .. 128 (residual and Jacobian), and ``large_exp_hessian=True`` beside them serves its Hessian of the
-    Lagrangian as well -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work; without ``large_exp=True`` it is a ``ValueError``."""
+    Lagrangian as well -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work; without ``large_exp=True`` it is a ``ValueError``.
+    ``large_exp_reduce=True`` beside ``large_exp=True`` serves the compact Jacobian and the merit / reduce payload there (a ``ValueError`` without it)."""
     if isinstance(system, (list, tuple)):
         from .quantum import OpenQuantumSystem
         from .trajectory import DENSITY

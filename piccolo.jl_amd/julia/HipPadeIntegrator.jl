@@ -87,7 +87,13 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
                       x_offs::Vector{Int32}, global_dim::Int; device::Integer = 0, pade_order::Integer = 4, state_cols::Integer = 0,
                       exp_hessian::Bool = false, exp_full::Bool = false, large_generator::Bool = false,
                       large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false,
-                      large_exp_hessian::Bool = false)
+                      large_exp_hessian::Bool = false, large_exp_reduce::Bool = false)
+    # large_exp_reduce = true (with large_exp = true only): the library's option large_exp_reduce -- pcl_jac_compact_nnz, pcl_eval_jac_compact_dev,
+    # pcl_jac_expand_dev, pcl_merit_grad_len, pcl_merit_grad_dev, pcl_eval_jac_merit_dev and the host-pointer calls' compact route are served on the
+    # exponential constraint at generator dimensions 66 .. 128 (compact layout [-E | tails] per interval).  At n <= 64 it sets nothing (exp_full is
+    # that context's switch).  Never set on its own.
+    (large_exp_reduce && !large_exp) &&
+        throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is the compact Jacobian and the reduce payload of a context created with large_exp = true (large_generator = true, pade_order = :exp): it needs that keyword"))
     # large_exp_hessian = true (with large_exp = true only, hence large_generator = true and pade_order = :exp): the library's option large_exp_hess --
     # the Hessian of the Lagrangian of the exponential constraint at generator dimensions 66 .. 128 (hess_per > 0, eval_hessian = true works).  At
     # n <= 64 it sets nothing (exp_hessian is that context's switch).  Never set on its own.
@@ -153,6 +159,7 @@ function _create_core(G0s::Vector{Matrix{Float64}}, Gjs::Vector{Matrix{Float64}}
     (large && large_exp && large_exp_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_exp_hess", 1))
     (large && large_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_full", 1))
     (large && large_reduce) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_reduce", 1))
+    (large && large_exp && large_exp_reduce) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_exp_reduce", 1))
     served = large ? (large_exp ? large_exp_hessian : large_hessian) : (pade_order != PCL_ORDER_EXP || exp_hessian)
     !served ? (nnz[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, nnz, per))
     core = PclCore(c, M, Int(xd[]), Int(nr[]) ÷ M, jac_per, Int(nnz[]) ÷ M, Float64[], Float64[], Float64[], false, false, 0)
@@ -223,7 +230,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
-const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true
+const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true, compact Jacobian and reduce payload with large_exp_reduce = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
 
@@ -324,7 +331,8 @@ end
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
                       var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false,
-                      large_exp_hessian::Bool = false)
+                      large_exp_hessian::Bool = false, large_exp_reduce::Bool = false)
+    large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_reduce && throw(ArgumentError("HipPadeIntegrator: large_reduce = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)"))
