@@ -298,6 +298,33 @@ typedef enum pcl_status {
  * 323 after the payload-only launch (320 after the full-values launch with or without the payload's partial sums: "last_merit_fused" tells). */
 #define PCL_LARGE_EXP 0x200
 
+/* A third pcl_desc.batch_mode flag, beside PCL_LARGE_N: the variational (sensitivity) integrators -- PCL_BATCH_VARIATIONAL on the Pade
+ * constraint -- at generator dimensions 66 .. 128: robust control of the transmon-cavity sizes.  Chosen at creation only, never set on its own;
+ * pcl_create strips it as it strips the other two.  PCL_BATCH_VARIATIONAL[_EXP] | PCL_LARGE_N WITHOUT this flag keeps PCL_LARGE_N's refusal.
+ *   PCL_LARGE_VAR without PCL_LARGE_N, or with PCL_BATCH_MEMBERS / PCL_BATCH_TRAJ           PCL_EINVAL
+ *   PCL_LARGE_VAR with PCL_BATCH_VARIATIONAL_EXP or with PCL_LARGE_EXP                      PCL_ENOTIMPL naming PCL_LARGE_VAR
+ *   PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, n <= 64                            the ordinary variational context: same kernels, same bits
+ *   the same, 66 <= n <= 128 (n = 2d is even), v = 1 or 2, m <= 24, state_cols d or 1,
+ *     pade_order 0 / 2 / 4 / 6 / 8 / 10                                                     a LARGE VARIATIONAL context
+ *   the same, n > 128                                                                       PCL_ESHAPE with the byte counts, as for PCL_LARGE_N
+ * -- all decided before the device is touched.  Such a context runs one kernel (pcl_kernel_var_large.hpp, on the one-tile plan of the large
+ * family: chain workgroups per (interval, slice of state columns, drive group) carry W, V and the dW_l of all 1 + v components, panel workgroups
+ * carry the powers of G and, one variation at a time, its Frechet powers).  Rows, value order, layout and structure are exactly
+ * those of PCL_BATCH_VARIATIONAL at n <= 64: (2 + 4v) C n^2 + x_dim (m + 1) values per interval.  No atomics: every work split, two launches
+ * and the residual-only launch against the fused launch's residual give the same bits; component 0 (delta_0, its tails, every -B+ | B- copy) has
+ * the bits of a plain PCL_LARGE_N context of the same drift and drives.
+ * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
+ * (host-pointer calls deliver full values), streams and sync, options, pcl_deriv_*, and pade_order = 0 with pcl_set_order_policy /
+ * pcl_set_order_from_trajectory (theta of the lifted generator, host arithmetic on up to 384 x 384).  PCL_ENOTIMPL, each message naming
+ * PCL_LARGE_VAR: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64], the options "var_full" = 1 (and the objective family and rollout behind
+ * it) and "var_compact" = 1 (and the compact trio), the merit / reduce entry points, the member window, pcl_infidelity_dev.  The options
+ * "large_hess", "large_full", "large_reduce", "large_exp_hess", "large_exp_reduce" = 1 are PCL_EINVAL, as on every context that is not of
+ * their kind.
+ * Options: "cols_per_slice" caps the state columns per chain workgroup, "general_slices" sets the least number of panel workgroups per role,
+ * "var_large_drives" caps the drives per group (0 auto; PCL_EINVAL when negative or off such a context); "var_block_wgs" / "var_col_wgs" have
+ * no effect.  get_option "last_kernel" reads 340 + q after a residual + Jacobian launch and 350 + q after a residual-only launch. */
+#define PCL_LARGE_VAR 0x400
+
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
     int32_t d;           /* Hilbert-space dimension (sys.levels); n = 2d, x_dim = 2 d^2 */

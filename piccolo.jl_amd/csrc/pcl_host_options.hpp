@@ -40,7 +40,13 @@ extern "C" int pcl_set_option(pcl_ctx *ctx, const char *key, int64_t v) {
     else if (!strcmp(key, "var_compact")) {  // variational contexts, either constraint kind: serve the compact Jacobian trio and the host expansion (0: refuse them, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_compact must be 0 or 1");
         if (v && !ctx->var) return fail(ctx, PCL_EINVAL, "var_compact = 1 needs a variational context (PCL_BATCH_VARIATIONAL or PCL_BATCH_VARIATIONAL_EXP)");
+        if (v && ctx->large_var)
+            return fail(ctx, PCL_ENOTIMPL, "var_compact = 1 is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", ctx->n);
         ctx->var_compact = (int)v;
+    }
+    else if (!strcmp(key, "var_large_drives")) {  // large variational contexts: the most drives per group of the residual + Jacobian launch (0 auto: all of them where they fit)
+        if (v < 0 || !ctx->large_var) return fail(ctx, PCL_EINVAL, "var_large_drives must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)");
+        ctx->opt_var_large_drives = v;
     }
     else if (!strcmp(key, "var_exp_hess")) {  // variational contexts of the exponential constraint: serve the Hessian of the Lagrangian (0: refuse it, the default)
         if (v != 0 && v != 1) return fail(ctx, PCL_EINVAL, "var_exp_hess must be 0 or 1");
@@ -240,6 +246,10 @@ extern "C" int pcl_get_option(const pcl_ctx *ctx, const char *key, int64_t *v) {
         *v = ctx->exp_full;
     else if (!strcmp(key, "var_compact"))
         *v = ctx->var_compact;
+    else if (!strcmp(key, "var_large_drives"))
+        *v = ctx->opt_var_large_drives;
+    else if (!strcmp(key, "large_variational"))  // 1: a large variational context (PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64)
+        *v = ctx->large_var;
     else if (!strcmp(key, "var_exp_hess"))
         *v = ctx->var_exp_hess;
     else if (!strcmp(key, "var_exp_hess_tiles"))

@@ -23,6 +23,8 @@ static void var_drop_objective(pcl_ctx *ctx) {
 static int var_set_full(pcl_ctx *ctx, int64_t on) {
     if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "var_full must be 0 or 1");
     if (!ctx->var) return on ? fail(ctx, PCL_EINVAL, "var_full = 1 needs a variational context (PCL_BATCH_VARIATIONAL)") : PCL_OK;
+    if (on && ctx->large_var)
+        return fail(ctx, PCL_ENOTIMPL, "var_full = 1 is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", ctx->n);
     if ((int)on == ctx->var_full) return PCL_OK;
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

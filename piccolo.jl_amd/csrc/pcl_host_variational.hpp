@@ -7,6 +7,7 @@
 #include "pcl_kernel_var_exp.hpp"
 #include "pcl_kernel_var_exp_hess.hpp"
 #include "pcl_kernel_var_exp_hess_tiles.hpp"
+#include "pcl_kernel_var_large.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
@@ -16,7 +17,8 @@ static long long var_jac_per(const pcl_ctx *c) {
 }
 
 // Validation of a variational descriptor: every check runs before any device call; the message names the field.
-static int var_validate(const pcl_desc *D) {
+// large_var: the descriptor carried PCL_LARGE_N | PCL_LARGE_VAR (generator dimensions up to PCL_LARGE_MAX_N on the Pade constraint)
+static int var_validate(const pcl_desc *D, bool large_var) {
     const int d = D->d, m = D->n_drives;
     if (D->batch < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: batch=%d; PCL_BATCH_VARIATIONAL takes batch = 1 + v with v >= 1 variations", D->batch);
     if (D->per_member_G0 != 1)
@@ -54,7 +56,10 @@ static int var_validate(const pcl_desc *D) {
             return fail(nullptr, PCL_EINVAL, "pcl_create: x_offs[%d]=%d overlaps u_off / dt_off", b, D->x_offs[b]);
     }
     // shapes the kernels take
-    if (d > PCL_MAX_D) return fail(nullptr, PCL_ESHAPE, "pcl_create: d=%d exceeds %d (LDS-resident generator tiles)", d, PCL_MAX_D);
+    if (large_var && 2 * d > PCL_LARGE_MAX_N)
+        return fail(nullptr, PCL_ESHAPE, "pcl_create: generator dimension %d exceeds %d, the most PCL_LARGE_N | PCL_LARGE_VAR serves: one n x n LDS tile would take %zu B of the 163840 B a workgroup can have (132096 B at n = %d)",
+                    2 * d, PCL_LARGE_MAX_N, (size_t)((2 * d) | 1) * (2 * d) * sizeof(double), PCL_LARGE_MAX_N);
+    if (d > PCL_MAX_D && !large_var) return fail(nullptr, PCL_ESHAPE, "pcl_create: d=%d exceeds %d (LDS-resident generator tiles)", d, PCL_MAX_D);
     if (D->batch - 1 > PCL_VAR_MAXV) return fail(nullptr, PCL_ESHAPE, "pcl_create: %d variations; PCL_BATCH_VARIATIONAL takes at most %d", D->batch - 1, PCL_VAR_MAXV);
     if (m > 24) return fail(nullptr, PCL_ESHAPE, "pcl_create: n_drives=%d exceeds 24", m);
     return PCL_OK;
@@ -68,8 +73,8 @@ static size_t var_exp_lds_bytes(int n, size_t max_lds, int *g_lds) {
     return six ? five + tile : five;
 }
 
-static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
-    if (int rc = var_validate(dsc)) return rc;
+static int var_create(const pcl_desc *dsc, pcl_ctx **out, bool large_var_flag = false) {
+    if (int rc = var_validate(dsc, large_var_flag)) return rc;
     const int d = dsc->d, m = dsc->n_drives, n = 2 * d, v = dsc->batch - 1;
     const int cols = dsc->state_cols > 0 ? dsc->state_cols : d;
     int ndev = 0;
@@ -83,6 +88,7 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
     ctx->desc = *dsc;
     ctx->var = v;
     ctx->vexp = dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP ? 1 : 0;
+    ctx->large_var = large_var_flag && n > 2 * PCL_MAX_D ? 1 : 0;  // (the flags at n <= 64: the ordinary variational context)
     ctx->n = n;
     ctx->K = dsc->N - 1;
     ctx->cols = cols;
@@ -196,6 +202,48 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out) {
         g_create_error = ctx->err;
         pcl_destroy(ctx);
         return PCL_EHIP;
+    }
+    if (ctx->large_var) {
+        // the tables of pcl_var_large_kernel.  The drives as a plain large context has them, so that G(u_k) and the drive terms of component 0 go
+        // through its operations: the union pattern with its coefficient table (build_G) and the rows [l][i][ell_w]; the variation generators in
+        // rows of the same form, [b][i][vl_gw] (a dense Gv_i is a row of width n)
+        std::vector<int> upos, ecol, gcol;
+        std::vector<double> ucoef, evalv, gval;
+        for (size_t pz = 0; pz < nn; ++pz) {
+            bool any = false;
+            for (int l = 0; l < m; ++l) any |= dsc->Gj[l * nn + pz] != 0.0;
+            if (any) {
+                upos.push_back((int)pz);
+                for (int l = 0; l < m; ++l) ucoef.push_back(dsc->Gj[l * nn + pz]);
+            }
+        }
+        ctx->n_upos = (int)upos.size();
+        auto rows_of = [&](const double *A, int cnt, int floor_w, std::vector<int> &col, std::vector<double> &val) {
+            int wd = floor_w;
+            for (int t = 0; t < cnt; ++t)
+                for (int i = 0; i < n; ++i) {
+                    int c = 0;
+                    for (int j = 0; j < n; ++j) c += A[t * nn + i + (size_t)n * j] != 0.0;
+                    wd = std::max(wd, c);
+                }
+            col.assign((size_t)cnt * n * wd, 0);
+            val.assign((size_t)cnt * n * wd, 0.0);
+            for (int t = 0; t < cnt; ++t)
+                for (int i = 0; i < n; ++i) {
+                    size_t e = ((size_t)t * n + i) * wd;
+                    for (int j = 0; j < n; ++j)
+                        if (A[t * nn + i + (size_t)n * j] != 0.0) col[e] = j, val[e] = A[t * nn + i + (size_t)n * j], ++e;
+                }
+            return wd;
+        };
+        ctx->ell_w = rows_of(dsc->Gj, m, m > 0 ? 1 : 0, ecol, evalv);
+        ctx->vl_gw = rows_of(dsc->G0 + nn, v, 1, gcol, gval);
+        if (upload(ctx, &ctx->dupos, upos) != PCL_OK || upload(ctx, &ctx->ducoef, ucoef) != PCL_OK || upload(ctx, &ctx->dell_col, ecol) != PCL_OK ||
+            upload(ctx, &ctx->dell_val, evalv) != PCL_OK || upload(ctx, &ctx->dvl_gcol, gcol) != PCL_OK || upload(ctx, &ctx->dvl_gval, gval) != PCL_OK) {
+            g_create_error = ctx->err;
+            pcl_destroy(ctx);
+            return PCL_EHIP;
+        }
     }
     VAR_HIP(hipHostMalloc((void **)&ctx->herr, 64, hipHostMallocMapped));
     *ctx->herr = 0;
@@ -543,11 +591,128 @@ static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, 
     return PCL_OK;
 }
 
+// Large variational kernel (pcl_kernel_var_large.hpp; contexts created with PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR).  The plan, every
+// branch from (n, C, m, v, intervals, CUs, options): LD = n | 1, 64 threads per 16-row tile of G; what the one tile leaves of the LDS is NB column
+// blocks of LD doubles.  A chain unit takes nc state columns and mg drives of all 1 + v components: (1 + v) nc (2 + 2 (2 + mg)) blocks with the
+// Jacobian (-S, D, and W | V | dW_l twice), (1 + v) nc 4 without.  Every group forms W and V again, so the widest nc at which ALL drives (option
+// var_large_drives caps them) fit one group is taken (option cols_per_slice caps it); where not even one column takes them all, one column and the
+// most drives that fit, evened over the groups (n = 128, v = 2: one column, one drive, 24 of the 29 blocks).  Launches of few intervals take
+// narrower slices while the chain units stay within half a round of the CUs.  Panel units are workgroups of their own, (1 + v) pu of them: npc
+// columns of the powers need three blocks each (P', Q, Q') and a thread owns at most PL_NP pairs; one unit per 16 columns at least (option
+// general_slices: that many units per role at least).  Every split gives the same bits.
+struct VarLargePlan {
+    int LD, threads, NB, sx, nc, mg, ngrp, chain_units, chain_blocks, npc, pu, U;
+    size_t lds;
+};
+static void var_large_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, bool jac, long long items, VarLargePlan &P) {
+    const int comp = 1 + v;
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
+    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
+    const int mg_cap = jac && m > 0 ? (ctx->opt_var_large_drives > 0 ? (int)std::min<int64_t>(ctx->opt_var_large_drives, m) : m) : 0;
+    auto blocks = [&](int nc, int mg) { return comp * nc * (jac ? 2 + 2 * (2 + mg) : 4); };
+    P.nc = 1;
+    for (int nc = nc_cap; nc > 1; --nc)
+        if (blocks(nc, mg_cap) <= P.NB) {
+            P.nc = nc;
+            break;
+        }
+    P.mg = mg_cap;
+    while (P.mg > 1 && blocks(P.nc, P.mg) > P.NB) --P.mg;  // (one column only: the most drives that fit)
+    P.ngrp = mg_cap > 0 ? (m + P.mg - 1) / P.mg : 1;
+    if (mg_cap > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
+    P.sx = (cols + P.nc - 1) / P.nc;
+    const long long want_sx = ctx->n_cu / std::max(2 * items * P.ngrp, 1LL);
+    if (want_sx > P.sx) P.sx = (int)std::min<long long>(want_sx, cols);
+    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.sx = (cols + P.nc - 1) / P.nc;  // (no unit without work)
+    P.chain_units = P.sx * P.ngrp;
+    P.chain_blocks = blocks(P.nc, P.mg);
+    P.npc = P.pu = 0;
+    if (jac) {
+        auto fits = [&](int pu) {
+            const int npc = (n + pu - 1) / pu;
+            return 3 * npc <= P.NB && ((long long)n * npc + 1) / 2 <= (long long)PL_NP * P.threads;
+        };
+        P.pu = 1;
+        while (P.pu < n && !fits(P.pu)) ++P.pu;
+        const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices : (n + 15) / 16;
+        P.pu = (int)std::max<long long>(P.pu, std::min<long long>(want, n));
+        P.npc = (n + P.pu - 1) / P.pu;
+        P.pu = (n + P.npc - 1) / P.npc;  // (no unit without work)
+    }
+    P.U = P.chain_units + comp * P.pu;
+    P.lds = (size_t)(fixed + (long long)P.LD * std::max(P.chain_blocks, 3 * P.npc)) * sizeof(double);
+}
+static int var_large_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var;
+    const bool jac = vals != nullptr;
+    VarLargePlan P;
+    var_large_plan(ctx, n, ctx->cols, m, v, jac, ctx->K, P);
+    if (P.lds > (size_t)ctx->max_lds || P.chain_blocks > P.NB)
+        return fail(ctx, PCL_ESHAPE, "the large variational kernel needs %zu B of LDS (> %d) for n = %d, m = %d, v = %d", P.lds, ctx->max_lds, n, m, v);
+    KParams p;
+    memset(&p, 0, sizeof p);
+    fill_pade(p, D.pade_order);
+    p.Z = Z;
+    p.delta = delta;
+    p.jac = vals;
+    p.G0 = ctx->dvar_tab;
+    p.upos = ctx->dupos;
+    p.ucoef = ctx->ducoef;
+    p.n_upos = ctx->n_upos;
+    p.ell_val = ctx->dell_val;
+    p.ell_col = ctx->dell_col;
+    p.ell_w = ctx->ell_w;
+    p.x_off0 = -1;
+    p.jac_per = var_jac_per(ctx);
+    p.d = D.d;
+    p.n = n;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.batch = 1;
+    p.cols = ctx->cols;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.LD = P.LD;
+    p.nt = ctx->opt_nt == 1 ? 1 : 0;  // (plain or nontemporal block stores)
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    VarLargeParams w;
+    memset(&w, 0, sizeof w);
+    w.Gv = ctx->dvar_tab + (size_t)(1 + m) * n * n;
+    w.gv_val = ctx->dvl_gval;
+    w.gv_col = ctx->dvl_gcol;
+    w.gv_w = ctx->vl_gw;
+    w.v = v;
+    for (int b = 0; b <= v; ++b) w.xo[b] = ctx->x_offs[b];
+    w.sx = P.sx;
+    w.mg = P.mg;
+    w.ngrp = P.ngrp;
+    w.npc = P.npc;
+    w.pu = P.pu;
+    const long long grid = (long long)ctx->K * P.U;
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
+    const void *f = jac ? (const void *)pcl_var_large_kernel<true> : (const void *)pcl_var_large_kernel<false>;
+    if (int rc = var_set_lds(ctx, f, P.lds)) return rc;
+    void *args[] = {&p, &w};
+    HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3((unsigned)P.threads), args, P.lds, ctx->stream));
+    ctx->last_kernel = (jac ? 340 : 350) + p.q;  // the large variational kernel: residual + Jacobian | residual only
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
 static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals, bool compact = false) {
     ON_DEVICE(ctx);
     if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals, compact);
     if (ctx->desc.pade_order == 0)
         return fail(ctx, PCL_EINVAL, "pcl_eval / pcl_jac: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
+    if (ctx->large_var) return var_large_launch(ctx, Z, delta, vals);
     VarParams p;
     var_fill(ctx, p);
     p.Z = Z;
@@ -603,8 +768,16 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
     return PCL_OK;
 }
 
+// A large variational context (PCL_LARGE_N | PCL_LARGE_VAR, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is
+// refused in these words
+#define LARGE_VAR_NOTIMPL(ctx, what)                                                                                                   \
+    do {                                                                                                                               \
+        if ((ctx) && (ctx)->large_var)                                                                                                 \
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
+    } while (0)
 #define VAR_NOTIMPL(ctx, what)                                                                                                         \
     do {                                                                                                                               \
+        LARGE_VAR_NOTIMPL(ctx, what);                                                                                                  \
         if ((ctx) && (ctx)->var)                                                                                                       \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (%s)", what, (ctx)->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL"); \
     } while (0)

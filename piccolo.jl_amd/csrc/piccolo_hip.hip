@@ -7,6 +7,7 @@
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
 //   pcl_kernel_large_exp_hess.hpp   ... its Hessian of the Lagrangian (option large_exp_hess): the adjoint of that recurrence with the second derivative carried, per-column partial sums
+//   pcl_kernel_var_large.hpp        ... the variational integrators there (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR): chain units of 1 + v components, panel units of the powers and, one variation at a time, the Frechet powers
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
@@ -111,6 +112,11 @@ struct pcl_ctx {
     int var_wG = 0, var_wD = 0, var_wV = 0;
     long long var_off_d = 0, var_voff_d = 0, var_off_v = 0, var_voff_v = 0;
     int64_t opt_var_blocks = 0, opt_var_cols = 0;  // ... block / column workgroups per interval of the fused launch (0 auto)
+    int large_var = 0;                    // ... PCL_LARGE_N | PCL_LARGE_VAR with 66 <= n <= 128: every residual / Jacobian launch is pcl_var_large_kernel (pcl_kernel_var_large.hpp); everything else is refused; its tables are dupos / ducoef / dell_* (the drives, as a plain large context has them) and the two below
+    int64_t opt_var_large_drives = 0;     // ... ... the most drives per group of that launch (0 auto: all of them where they fit)
+    int *dvl_gcol = nullptr;              // ... ... the variation generators row-compressed, [v][n][vl_gw] (row-major, zero padded)
+    double *dvl_gval = nullptr;
+    int vl_gw = 0;
     int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
     int var_compact = 0;         // ... option var_compact: the compact Jacobian trio and the host expansion are served (either constraint kind)
     std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
@@ -415,6 +421,7 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension %d > 64): residual and Jacobian, and by option large_full the objective and the rollout", what, (ctx)->n); \
         if ((ctx) && (ctx)->large)                                                                                                                        \
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
+        LARGE_VAR_NOTIMPL(ctx, what);                                                                                                                     \
     } while (0)
 
 // ... its Hessian of the Lagrangian by option large_hess only (pcl_kernel_pade_large_hess.hpp; a large exponential context: by option large_exp_hess,
@@ -454,17 +461,26 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
-    // PCL_LARGE_N and PCL_LARGE_EXP: stripped here, once; everything below (and the context) sees the plain batch mode
+    // PCL_LARGE_N, PCL_LARGE_EXP and PCL_LARGE_VAR: stripped here, once; everything below (and the context) sees the plain batch mode
     const bool large_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_N) != 0;
     const bool large_exp_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_EXP) != 0;
+    const bool large_var_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_VAR) != 0;
     pcl_desc plain_desc = *dsc;
-    if (large_flag || large_exp_flag) {
-        plain_desc.batch_mode &= ~(PCL_LARGE_N | PCL_LARGE_EXP);
+    if (large_flag || large_exp_flag || large_var_flag) {
+        plain_desc.batch_mode &= ~(PCL_LARGE_N | PCL_LARGE_EXP | PCL_LARGE_VAR);
         dsc = &plain_desc;
+        if (large_var_flag && !large_flag)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR goes with PCL_LARGE_N (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, a diagonal Pade order)");
+        if (large_var_flag && dsc->batch_mode != PCL_BATCH_VARIATIONAL && dsc->batch_mode != PCL_BATCH_VARIATIONAL_EXP)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR is the variational integrators at generator dimensions 66 .. %d: it goes with PCL_BATCH_VARIATIONAL, not with batch_mode %d (PCL_BATCH_MEMBERS and PCL_BATCH_TRAJ take PCL_LARGE_N alone)",
+                        PCL_LARGE_MAX_N, dsc->batch_mode);
+        if (large_var_flag && (dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP || large_exp_flag || dsc->pade_order == PCL_ORDER_EXP))
+            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_VAR is not implemented for the exponential constraint (%s); it serves PCL_BATCH_VARIATIONAL at the diagonal Pade orders 2 .. 10",
+                        dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP ? "batch_mode PCL_BATCH_VARIATIONAL_EXP" : large_exp_flag ? "the flag PCL_LARGE_EXP" : "pade_order = PCL_ORDER_EXP");
         if (large_exp_flag && !large_flag)
             return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_EXP goes with PCL_LARGE_N (batch_mode | PCL_LARGE_N | PCL_LARGE_EXP, pade_order = PCL_ORDER_EXP)");
-        if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP)
-            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the variational integrators (batch_mode %s); it goes with PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ",
+        if (!large_var_flag && (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP))
+            return fail(nullptr, PCL_ENOTIMPL, "pcl_create: PCL_LARGE_N is not implemented for the variational integrators (batch_mode %s); it goes with PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ -- and with PCL_BATCH_VARIATIONAL on the Pade constraint by the flag PCL_LARGE_VAR beside it",
                         dsc->batch_mode == PCL_BATCH_VARIATIONAL ? "PCL_BATCH_VARIATIONAL" : "PCL_BATCH_VARIATIONAL_EXP");
         if (large_exp_flag && dsc->pade_order != PCL_ORDER_EXP)
             return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_EXP is the exponential constraint at generator dimensions 66 .. %d: it needs pade_order = PCL_ORDER_EXP (got %d)", PCL_LARGE_MAX_N, dsc->pade_order);
@@ -473,7 +489,7 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     }
     if (dsc->batch_mode == PCL_BATCH_VARIATIONAL && dsc->pade_order == PCL_ORDER_EXP)
         return fail(nullptr, PCL_ENOTIMPL, "pcl_create: pade_order = PCL_ORDER_EXP (the exponential constraint) with batch_mode = PCL_BATCH_VARIATIONAL is not implemented; use batch_mode = PCL_BATCH_VARIATIONAL_EXP");
-    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP) return var_create(dsc, out);
+    if (dsc->batch_mode == PCL_BATCH_VARIATIONAL || dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP) return var_create(dsc, out, large_var_flag);
     const bool vec = dsc->state_cols == PCL_STATE_VECTOR;  // general real d x d generator on one real column
     const int d = dsc->d, m = dsc->n_drives, n = vec ? d : 2 * d;
     if (d < 1 || m < 0 || dsc->N < 2 || dsc->batch < 1)
@@ -776,7 +792,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart, ctx->dvl_gcol, ctx->dvl_gval};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);

@@ -159,13 +159,29 @@ def _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode=PCL_BATCH_ME
                          "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
 
 
+def _check_large_variational(large_variational, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
+    """The keyword ``large_variational`` (the library's flag ``PCL_LARGE_VAR``: the variational integrators at generator dimensions 66 .. 128) goes
+    with ``large_generator=True`` on a variational context of the Pade constraint: anything else is a ``ValueError``, before any device call."""
+    if not large_variational:
+        return
+    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP or batch_mode == PCL_BATCH_VARIATIONAL_EXP:
+        raise ValueError("large_generator=True on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" "
+                         "(PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts")
+    if batch_mode != PCL_BATCH_VARIATIONAL:
+        raise ValueError("large_variational=True is the flag PCL_LARGE_VAR of a variational context (VariationalUnitaryIntegrator / "
+                         "VariationalKetIntegrator with large_generator=True): a plain context takes large_generator=True alone")
+    if not large_generator:
+        raise ValueError("large_variational=True goes with large_generator=True (the flags PCL_LARGE_N | PCL_LARGE_VAR): it needs that keyword")
+
+
 class _PclContext:
     """Owns one ``pcl_ctx`` (one GPU, one stream)."""
 
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False):  # fmt: skip
+                 large_exp_reduce=False, large_variational=False):  # fmt: skip
+        _check_large_variational(large_variational, large_generator, pade_order, batch_mode)
         _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode)
         _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode)
         _check_large_exp(large_exp, large_generator, pade_order, batch_mode)
@@ -193,7 +209,7 @@ class _PclContext:
         xo = np.ascontiguousarray(np.asarray(x_offs, dtype=np.int32).reshape(-1))
         desc = _lib.pcl_desc(
             struct_size=ctypes.sizeof(_lib.pcl_desc), d=d, n_drives=m, N=N, z_dim=z_dim, u_off=u_off, dt_off=dt_off,
-            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0) | (_lib.PCL_LARGE_EXP if large_exp else 0), pade_order=pade_order, device_id=device,
+            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0) | (_lib.PCL_LARGE_EXP if large_exp else 0) | (_lib.PCL_LARGE_VAR if large_variational else 0), pade_order=pade_order, device_id=device,
             index_base=index_base, per_member_G0=int(bool(per_member_G0)), state_cols=state_cols, global_dim=global_dim,
             G0=g0.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
             Gj=gj.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
@@ -229,6 +245,9 @@ class _PclContext:
         # objective and the rollout by ``large_full``; the Hessian of the Lagrangian (unless ``large_exp_hessian``), the compact Jacobian and the
         # payload (unless ``large_exp_reduce``) raise
         self.large_exp = bool(large_exp) and self.large
+        # ``large_variational`` (the flag PCL_LARGE_VAR beside it, a variational context of the Pade constraint): residual and Jacobian there; the
+        # Hessian of the Lagrangian, ``var_full`` (objective, rollout) and ``var_compact`` raise with the library's message
+        self.large_variational = bool(large_variational) and self.large
         self.large_exp_hessian = False  # (``large_exp_hessian`` switches the library's option large_exp_hess on there: hess_nnz / hess_per follow it, set_option)
         self.large_exp_reduce = False  # (``large_exp_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
         self.large_hessian = False
@@ -831,11 +850,17 @@ class HipVariationalIntegrator:
 
     ``var_compact=True`` (any Pade order, or ``"exp"``) switches the library's option ``var_compact`` on: the compact Jacobian of the stacked
     state -- every distinct tile once, ``ctx.compact_per`` values per interval -- its device expansion, and the host-pointer calls' compact
-    path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself."""
+    path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself.
+
+    ``large_generator=True`` sets the library's flags ``PCL_LARGE_N | PCL_LARGE_VAR``: generator dimensions 66 .. 128 (a transmon with a cavity)
+    on the Pade constraint -- residual and Jacobian; ``hessian_structure`` / ``eval_hessian_of_lagrangian``, ``rollout`` and
+    ``enable_objective_and_rollout`` raise the library's message there (solve with a quasi-Newton Hessian).  At 64 and below it changes nothing.
+    With ``pade_order="exp"`` it is a ``ValueError``; never on by itself."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
-                 var_compact=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False):
+                 var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
+                 large_exp_hessian=False, large_exp_reduce=False):
+        _check_large_variational(large_generator, large_generator, pade_order, PCL_BATCH_VARIATIONAL)
         _check_large_exp_hessian(large_exp_hessian, large_exp, PCL_BATCH_VARIATIONAL)
         _check_large_exp_reduce(large_exp_reduce, large_exp, PCL_BATCH_VARIATIONAL)
         _check_large_exp(large_exp, False, pade_order, PCL_BATCH_VARIATIONAL)
@@ -877,6 +902,7 @@ class HipVariationalIntegrator:
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
             batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
+            large_generator=bool(large_generator), large_variational=bool(large_generator),
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)

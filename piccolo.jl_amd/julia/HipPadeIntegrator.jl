@@ -230,6 +230,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
+const PCL_LARGE_VAR = 1024  # (0x400) a third batch_mode flag beside PCL_LARGE_N (keyword large_generator of the variational integrators): PCL_BATCH_VARIATIONAL on the Pade constraint at generator dimensions 66 .. 128: residual and Jacobian
 const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true, compact Jacobian and reduce payload with large_exp_reduce = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
@@ -327,11 +328,14 @@ end
 #      var_compact = true (any order, or :exp): the library's option var_compact -- pcl_eval_jac / pcl_jac then deliver the Jacobian values
 #      through the compact ones (every distinct tile once over PCIe, replicated by the host's threads) where the blocks are replicated;
 #      off by default, never on by itself.
+#      large_generator = true: the library's flags PCL_LARGE_N | PCL_LARGE_VAR in batch_mode -- generator dimensions 66 .. 128 on the Pade
+#      constraint: residual and Jacobian; no Hessian of the Lagrangian (the structure stays empty, solve with eval_hessian = false), no
+#      objective or rollout from the library.  With pade_order = :exp: ArgumentError.  At 64 and below it changes nothing; never on by itself.
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
-                      var_compact::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false, large_exp::Bool = false,
-                      large_exp_hessian::Bool = false, large_exp_reduce::Bool = false)
+                      var_compact::Bool = false, large_generator::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false,
+                      large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false)
     large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
@@ -340,6 +344,8 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
+    (large_generator && expo) &&
+        throw(ArgumentError("HipPadeIntegrator: large_generator = true on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large variational contexts"))
     (exp_hessian isa Symbol && exp_hessian != :workspace) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian must be false, true or :workspace (got :$(exp_hessian))"))
     workspace = exp_hessian === :workspace
@@ -359,7 +365,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve G0s Gjv x_offs begin
         desc = PclDesc(sizeof(PclDesc), size(G0, 1) ÷ 2, m, traj.N, traj.dim, traj.components[u][1] - 1, traj.components[traj.timestep][1] - 1,
-                       length(names), expo ? 3 #= PCL_BATCH_VARIATIONAL_EXP =# : 2 #= PCL_BATCH_VARIATIONAL =#, pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
+                       length(names), (expo ? 3 #= PCL_BATCH_VARIATIONAL_EXP =# : 2 #= PCL_BATCH_VARIATIONAL =#) | (large_generator ? PCL_LARGE_N | PCL_LARGE_VAR : 0), pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
                        state_cols, traj.global_dim, pointer(G0s), pointer(Gjv), pointer(x_offs))
         rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
         rc == 0 || error("pcl_create: ", _lasterr(C_NULL))
@@ -371,7 +377,8 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     workspace && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess_tiles", 1))
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
     var_compact && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_compact", 1))
-    (expo && !exp_hessian) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    large_var = large_generator && size(G0, 1) > 64                   # (a large variational context: the Hessian of the Lagrangian is refused)
+    ((expo && !exp_hessian) || large_var) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
@@ -380,7 +387,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
     check(c, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, jr, jc))
     hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
-    (expo && !exp_hessian) || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
+    ((expo && !exp_hessian) || large_var) || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
     # (B.f is refused for the stacked state, see _f: fcore stays `nothing`)
     return HipPadeIntegrator(core, 1, x, names, u, core.x_dim, core.rows_per, jr, jc, hr, hc, Int(ncol[]), G0, Gj, state_cols, order, nothing)
 end
