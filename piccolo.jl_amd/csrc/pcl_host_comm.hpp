@@ -42,7 +42,7 @@ extern "C" int pcl_comm_get_unique_id(pcl_comm_id *out) {
     return nrc == 0 ? PCL_OK : rccl_fail(nullptr, "ncclGetUniqueId", nrc);
 }
 extern "C" int pcl_comm_init(pcl_ctx *ctx, const pcl_comm_id *id, int32_t rank, int32_t nranks) {
-    VAR_NOTIMPL(ctx, "pcl_comm_init");
+    TRY(require(ctx, FEAT_COLLECTIVE, "pcl_comm_init"));
     if (!ctx || !id) return PCL_EINVAL;
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(ctx, PCL_EINVAL, "pcl_comm_init: rank %d of %d", rank, nranks);
     if (ctx->comm) return fail(ctx, PCL_EINVAL, "pcl_comm_init: communicator already initialised");
@@ -56,7 +56,7 @@ extern "C" int pcl_comm_init(pcl_ctx *ctx, const pcl_comm_id *id, int32_t rank, 
     return PCL_OK;
 }
 extern "C" int pcl_reduce_sum_dev(pcl_ctx *ctx, double *buf_dev, int64_t n) {
-    VAR_NOTIMPL(ctx, "pcl_reduce_sum_dev");
+    TRY(require(ctx, FEAT_COLLECTIVE, "pcl_reduce_sum_dev"));
     if (!ctx) return PCL_EINVAL;
     if (!buf_dev || n < 0) return fail(ctx, PCL_EINVAL, "pcl_reduce_sum_dev: bad buffer");
     if (!ctx->comm) return fail(ctx, PCL_ERCCL, "pcl_reduce_sum_dev: call pcl_comm_init first");
@@ -65,7 +65,7 @@ extern "C" int pcl_reduce_sum_dev(pcl_ctx *ctx, double *buf_dev, int64_t n) {
     return nrc == 0 ? PCL_OK : rccl_fail(ctx, "ncclAllReduce", nrc);
 }
 extern "C" int pcl_reduce_sum(pcl_ctx *ctx, double *buf, int64_t n) {  // host buffer, staged through device memory; synchronous
-    VAR_NOTIMPL(ctx, "pcl_reduce_sum");
+    TRY(require(ctx, FEAT_COLLECTIVE, "pcl_reduce_sum"));
     if (!ctx) return PCL_EINVAL;
     if (!buf || n < 0) return fail(ctx, PCL_EINVAL, "pcl_reduce_sum: bad buffer");
     if (!ctx->comm) return fail(ctx, PCL_ERCCL, "pcl_reduce_sum: call pcl_comm_init first");

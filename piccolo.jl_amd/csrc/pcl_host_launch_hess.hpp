@@ -521,11 +521,9 @@ static int launch_hess_v1(pcl_ctx *ctx, KParams &p) {
 static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
-    LARGE_HESS_GATE(ctx, "pcl_hess");
+    TRY(require(ctx, FEAT_HESS, "pcl_hess"));
     if (ctx->large_exp) return launch_large_exp_hess(ctx, Z, mu, hess);
     if (ctx->large) return launch_pade_large_hess(ctx, Z, mu, hess);
-    VAR_EXP_NOHESS(ctx, "pcl_hess");
-    EXP_HESS_GATE(ctx, "pcl_hess");
     if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);
     if (ctx->vexp) return var_exp_launch_hess(ctx, Z, mu, hess);
     if (ctx->var) return var_launch_hess(ctx, Z, mu, hess);

@@ -895,11 +895,10 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_eval / pcl_jac")) return rc;
     if (ctx->var) {
-        if (compact && !ctx->var_compact) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a variational context (%s)", ctx->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL");
+        if (compact) TRY(require(ctx, FEAT_COMPACT, "the compact Jacobian"));  // (every other kind is refused at the entry point, or takes the host calls' full route)
         return var_launch_fused(ctx, Z, delta, jac, compact && jac);
     }
     if (int rc = resolve_order(ctx, nullptr, "pcl_eval / pcl_jac")) return rc;
-    if (ctx->exp && compact && !ctx->exp_full && !ctx->large_exp_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)");
     KParams p;
     fill_params(ctx, p);
     p.Z = window_Z(ctx, Z);
@@ -908,8 +907,7 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
     p.compact = compact ? 1 : 0;
     p.jac_per = compact ? jac_per_compact(ctx) : jac_per_full(ctx);
     const bool want_jac = jac != nullptr;
-    if (ctx->large_exp) {  // (without the option large_exp_reduce the compact Jacobian is refused at the entry points: LARGE_NOTIMPL)
-        if (compact && !ctx->large_exp_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP)");
+    if (ctx->large_exp) {
         if (want_jac && compact) return launch_large_exp(ctx, p, true, LE_COMPACT);
         // the payload-fused call (pcl_eval_jac_merit_dev, option large_exp_reduce): every member, so that the partial sums are numbered as the finish kernel reads them
         if (want_jac && ctx->large_exp_reduce && merit_call(ctx, p)) {
@@ -922,7 +920,6 @@ static int launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *ja
         return launch_large_exp(ctx, p, want_jac);
     }
     if (ctx->large) {
-        if (compact && !ctx->large_reduce) return fail(ctx, PCL_ENOTIMPL, "the compact Jacobian is not implemented for a context created with PCL_LARGE_N");
         if (want_jac && compact) return launch_pade_large(ctx, p, true, PL_COMPACT);
         // the payload-fused call (pcl_eval_jac_merit_dev, option large_reduce): every member, so that the partial sums are numbered as the finish kernel reads them
         if (want_jac && ctx->large_reduce && merit_call(ctx, p)) {

@@ -142,8 +142,7 @@ static int subspace_form(pcl_ctx *ctx, const double *gs, const int32_t *sub, int
     return set_form(ctx, 0, R, A.data(), nullptr, false);
 }
 extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c) {
-    LARGE_FULL_GATE(ctx, "pcl_set_goal_form");
-    VAR_GATE(ctx, "pcl_set_goal_form");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_set_goal_form"));
     if (ctx && ctx->var) return var_set_goal_form(ctx, scope, R, A, c);
     if (!ctx) return PCL_EINVAL;
     if (scope != 0 && scope != 1) return fail(ctx, PCL_EINVAL, "pcl_set_goal_form: scope must be 0 (per member) or 1 (joint)");
@@ -157,8 +156,7 @@ extern "C" int pcl_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const d
     return set_form(ctx, scope, R, A, c, true);
 }
 extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
-    LARGE_FULL_GATE(ctx, "pcl_set_goal");
-    VAR_GATE(ctx, "pcl_set_goal");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_set_goal"));
     if (ctx && ctx->var) return var_set_goal(ctx, goal_iso_vec);
     if (!ctx) return PCL_EINVAL;
     if (!goal_iso_vec) return fail(ctx, PCL_EINVAL, "pcl_set_goal: NULL");
@@ -174,8 +172,7 @@ extern "C" int pcl_set_goal(pcl_ctx *ctx, const double *goal_iso_vec) {
     return unitary_form(ctx, goal_iso_vec);
 }
 extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns) {
-    LARGE_FULL_GATE(ctx, "pcl_set_goal_subspace");
-    VAR_GATE(ctx, "pcl_set_goal_subspace");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_set_goal_subspace"));
     if (ctx && ctx->var) return var_set_goal_subspace(ctx, goal_sub_iso_vec, subspace, ns);
     if (!ctx) return PCL_EINVAL;
     if (!goal_sub_iso_vec || !subspace) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: NULL");
@@ -209,8 +206,7 @@ extern "C" int pcl_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_ve
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
 }
 extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
-    LARGE_FULL_GATE(ctx, "pcl_set_weights");
-    VAR_GATE(ctx, "pcl_set_weights");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_set_weights"));
     if (ctx && ctx->var) return var_set_weights(ctx, w);
     if (!ctx) return PCL_EINVAL;
     ON_DEVICE(ctx);
@@ -226,8 +222,7 @@ extern "C" int pcl_set_weights(pcl_ctx *ctx, const double *w) {
     return PCL_OK;
 }
 extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const double *R, int32_t dt_power) {
-    LARGE_FULL_GATE(ctx, "pcl_add_regularizer");
-    VAR_GATE(ctx, "pcl_add_regularizer");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_add_regularizer"));
     if (!ctx) return PCL_EINVAL;
     if (!R || dim < 1 || off < 0 || off + dim > ctx->desc.z_dim) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: component [%d, %d) outside the knot (z_dim=%d)", off, off + dim, ctx->desc.z_dim);
     if (dt_power < 0 || dt_power > 2) return fail(ctx, PCL_EINVAL, "pcl_add_regularizer: dt_power must be 0, 1 or 2");
@@ -239,8 +234,7 @@ extern "C" int pcl_add_regularizer(pcl_ctx *ctx, int32_t off, int32_t dim, const
     return PCL_OK;
 }
 extern "C" int pcl_clear_regularizers(pcl_ctx *ctx) {
-    LARGE_FULL_GATE(ctx, "pcl_clear_regularizers");
-    VAR_GATE(ctx, "pcl_clear_regularizers");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_clear_regularizers"));
     if (!ctx) return PCL_EINVAL;
     ctx->regs.clear();
     ctx->reg_R.clear();
@@ -254,8 +248,7 @@ static int infidelity_lds_attr(pcl_ctx *ctx, const void *kern, size_t lds) {
     return PCL_OK;
 }
 extern "C" int pcl_infidelity_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_FULL_GATE(ctx, "pcl_infidelity_dev");
-    VAR_NOTIMPL(ctx, "pcl_infidelity_dev");
+    TRY(require(ctx, FEAT_INFIDELITY, "pcl_infidelity_dev"));
     if (!ctx) return PCL_EINVAL;
     if (!Z || (!value && !grad)) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_infidelity_dev: call pcl_set_goal first");
@@ -303,8 +296,7 @@ static int objective_prepare(pcl_ctx *ctx) {
 static bool tail_applies(const pcl_ctx *ctx, const double *grad, int &lo_, int &hi_);
 static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad, int skip_lo, int skip_hi, double *merit_out);
 extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_FULL_GATE(ctx, "pcl_objective_dev");
-    VAR_GATE(ctx, "pcl_objective_dev");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective_dev"));
     if (ctx && ctx->var) return var_objective_dev(ctx, Z, Q, value, grad);
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective_dev: NULL pointer");
@@ -363,8 +355,7 @@ extern "C" int pcl_objective_dev(pcl_ctx *ctx, const double *Z, double Q, double
     return PCL_OK;
 }
 extern "C" int pcl_objective(pcl_ctx *ctx, const double *Z, double Q, double *value, double *grad) {
-    LARGE_FULL_GATE(ctx, "pcl_objective");
-    VAR_GATE(ctx, "pcl_objective");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective"));
     if (!ctx) return PCL_EINVAL;
     if (!Z || !value) return fail(ctx, PCL_EINVAL, "pcl_objective: NULL pointer");
     ON_DEVICE(ctx);
@@ -472,9 +463,7 @@ static int launch_large_exp_payload(pcl_ctx *ctx, const double *Z, const double 
 }
 // [phi | J^T lam on the shared controls and time steps]: the payload of the one collective (pcl_reduce_sum_dev)
 extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const double *lam, const double *vals, double *out) {
-    LARGE_REDUCE_GATE(ctx, "pcl_merit_grad_dev");
-    VAR_NOTIMPL(ctx, "pcl_merit_grad_dev");
-    EXP_FULL_GATE(ctx, "pcl_merit_grad_dev");
+    TRY(require(ctx, FEAT_MERIT, "pcl_merit_grad_dev"));
     if (!ctx) return PCL_EINVAL;
     if (!delta || !vals || !out) return fail(ctx, PCL_EINVAL, "pcl_merit_grad_dev: NULL pointer");
     ON_DEVICE(ctx);
@@ -490,14 +479,12 @@ extern "C" int pcl_merit_grad_dev(pcl_ctx *ctx, const double *delta, const doubl
 }
 // fused residual + Jacobian + reduce payload: one pass over the state columns (the tails are not read back from HBM)
 extern "C" int pcl_eval_jac_merit_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out) {
-    LARGE_REDUCE_GATE(ctx, "pcl_eval_jac_merit_dev");
-    VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_dev");
+    if (ctx && kind_of(ctx) == KIND_EXP && !serves(ctx, FEAT_MERIT) && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
+    TRY(require(ctx, FEAT_MERIT, "pcl_eval_jac_merit_dev"));
     if (ctx && ctx->large && Z && delta && out && !vals) {  // the payload alone: no Jacobian value is formed (vals may be NULL under large_reduce / large_exp_reduce)
         ctx->merit_fused = 0;
         return ctx->large_exp ? launch_large_exp_payload(ctx, Z, lam, delta, out) : launch_large_payload(ctx, Z, lam, delta, out);
     }
-    if (ctx && ctx->exp && !ctx->exp_full && Z && delta && out && !vals) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_dev: NULL pointer");  // (vals may be NULL under exp_full only)
-    EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_dev");
     if (!ctx) return PCL_EINVAL;
     if (Z && delta && out && !vals && ctx->exp_full) {  // the payload alone: no Jacobian value is formed
         ctx->merit_fused = 0;
@@ -565,22 +552,9 @@ static int obj_hess_alloc(pcl_ctx *ctx, double **buf, long long count, const cha
     (void)hipGetLastError();
     return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "%s (%lld doubles): %s", what, count, hipGetErrorString(e));
 }
-// option large_reduce (large contexts): 1 serves the compact Jacobian trio, the host-pointer calls' compact route and the merit / reduce entry points;
-// 0 refuses them again.  Never on by itself; any other context refuses 1 and reads 0
-static int large_set_reduce(pcl_ctx *ctx, int64_t on) {
-    if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "large_reduce must be 0 or 1");
-    if (on && !ctx->large)
-        return fail(ctx, PCL_EINVAL, "large_reduce = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64, on the Pade constraint); every other context serves its compact Jacobian and reduce payload without it or by an option of its own");
-    ctx->large_reduce = (int)on;
-    return PCL_OK;
-}
 // option large_full (large contexts): 1 serves the objective family and the rollout; 0 refuses them again and drops goal, weights and regularisers
 static int large_set_full(pcl_ctx *ctx, int64_t on) {
-    if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "large_full must be 0 or 1");
-    if (!ctx->large)
-        return on ? fail(ctx, PCL_EINVAL, "large_full = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64, on the Pade constraint); every other context serves its objective and rollout without it or by an option of its own")
-                  : PCL_OK;
-    if ((int)on == ctx->large_full) return PCL_OK;
+    if ((int)on == ctx->large_full) return PCL_OK;  // (set_gate has checked the value and the kind of context)
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (double **q : {&ctx->dgoal, &ctx->dweights, &ctx->dformA, &ctx->dformc, &ctx->dgram, &ctx->dcoef}) {
@@ -599,8 +573,7 @@ static int large_set_full(pcl_ctx *ctx, int64_t on) {
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
-    LARGE_FULL_GATE(ctx, "pcl_objective_hess_nnz");
-    VAR_GATE(ctx, "pcl_objective_hess_nnz");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective_hess_nnz"));
     if (ctx && ctx->var) return var_objective_hess_nnz(ctx, nnz);
     if (!ctx || !nnz) return PCL_EINVAL;
     const int nbuf = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;
@@ -608,8 +581,7 @@ extern "C" int pcl_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz) {
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols) {
-    LARGE_FULL_GATE(ctx, "pcl_objective_hess_structure");
-    VAR_GATE(ctx, "pcl_objective_hess_structure");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective_hess_structure"));
     if (ctx && ctx->var) return var_objective_hess_structure(ctx, rows, cols);
     if (!ctx || !rows || !cols) return PCL_EINVAL;
     const pcl_desc &D = ctx->desc;
@@ -643,8 +615,7 @@ extern "C" int pcl_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, i
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    LARGE_FULL_GATE(ctx, "pcl_objective_hess_dev");
-    VAR_GATE(ctx, "pcl_objective_hess_dev");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective_hess_dev"));
     if (ctx && ctx->var) return var_objective_hess_dev(ctx, Z, Q, sigma, vals);
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess_dev: NULL pointer");
@@ -679,8 +650,7 @@ extern "C" int pcl_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, d
     return PCL_OK;
 }
 extern "C" int pcl_objective_hess(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals) {
-    LARGE_FULL_GATE(ctx, "pcl_objective_hess");
-    VAR_GATE(ctx, "pcl_objective_hess");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_objective_hess"));
     if (!ctx) return PCL_EINVAL;
     if (!Z || !vals) return fail(ctx, PCL_EINVAL, "pcl_objective_hess: NULL pointer");
     ON_DEVICE(ctx);
@@ -774,9 +744,7 @@ static int launch_tail(pcl_ctx *ctx, const double *Z, double Q, double *value, d
 // regulariser rows, the terminal infidelities and the payload's finish (pcl_ens_tail_kernel); the same bits as the separate calls.
 extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, const double *lam, double *delta, double *vals, double *out, double Q,
                                                 double *value, double *grad) {
-    if (ctx && !((ctx->large_reduce || ctx->large_exp_reduce) && ctx->large_full)) LARGE_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");  // (a large context: both options)
-    VAR_NOTIMPL(ctx, "pcl_eval_jac_merit_objective_dev");
-    EXP_FULL_GATE(ctx, "pcl_eval_jac_merit_objective_dev");
+    TRY(require(ctx, FEAT_STEP, "pcl_eval_jac_merit_objective_dev"));
     if (!ctx) return PCL_EINVAL;
     if (!Z || !delta || !vals || !out || !value) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: NULL pointer");
     if (!ctx->dgoal) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_merit_objective_dev: no goal set");
@@ -805,9 +773,7 @@ extern "C" int pcl_eval_jac_merit_objective_dev(pcl_ctx *ctx, const double *Z, c
     return PCL_OK;
 }
 extern "C" int pcl_merit_grad_len(const pcl_ctx *ctx, int64_t *len, int64_t *sets) {
-    LARGE_REDUCE_GATE(ctx, "pcl_merit_grad_len");
-    VAR_NOTIMPL(ctx, "pcl_merit_grad_len");
-    EXP_FULL_GATE(ctx, "pcl_merit_grad_len");
+    TRY(require(ctx, FEAT_MERIT, "pcl_merit_grad_len"));
     if (!ctx) return PCL_EINVAL;
     if (len) *len = 1 + (int64_t)ctx->K * ctx->desc.n_drives + ctx->K;
     if (sets) *sets = ctx->desc.batch_mode == PCL_BATCH_TRAJ ? ctx->desc.batch : 1;

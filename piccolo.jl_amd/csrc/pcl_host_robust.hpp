@@ -1,7 +1,7 @@
 // pcl_host_robust.hpp -- part of piccolo_hip.hip (included there, in place, after pcl_host_objective.hpp): what a variational context serves once
 // its option var_full is on -- the robust-control objective (terminal infidelity of the state, UnitarySensitivityObjective of the variations at
 // the terminal knot, regularisers on any component), its Hessian, and the rollout of the stacked state.  The entry points are the plain
-// contexts' (no new export); they hand over here behind VAR_GATE.
+// contexts' (no new export); they hand over here behind require(ctx, FEAT_OBJECTIVE).
 #pragma once
 static_assert(PCL_VAROBJ_MAXC == PCL_VAR_MAXV + 1, "components of a variational knot");
 
@@ -21,11 +21,7 @@ static void var_drop_objective(pcl_ctx *ctx) {
     ctx->regs_dirty = true;
 }
 static int var_set_full(pcl_ctx *ctx, int64_t on) {
-    if (on != 0 && on != 1) return fail(ctx, PCL_EINVAL, "var_full must be 0 or 1");
-    if (!ctx->var) return on ? fail(ctx, PCL_EINVAL, "var_full = 1 needs a variational context (PCL_BATCH_VARIATIONAL)") : PCL_OK;
-    if (on && ctx->large_var)
-        return fail(ctx, PCL_ENOTIMPL, "var_full = 1 is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", ctx->n);
-    if ((int)on == ctx->var_full) return PCL_OK;
+    if ((int)on == ctx->var_full) return PCL_OK;  // (set_gate has checked the value and the kind of context)
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (on && !ctx->dvar_coef) HIP_TRY(ctx, hipMalloc((void **)&ctx->dvar_coef, (size_t)(ctx->var + 1) * sizeof(double)));

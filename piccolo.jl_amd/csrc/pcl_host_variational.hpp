@@ -490,7 +490,6 @@ static long long var_exp_hess_part_per(const pcl_ctx *ctx) {
 }
 // option var_exp_hess = 1: the shape check, then the workspace (allocated here, on first use, not by pcl_create)
 static int var_exp_hess_enable(pcl_ctx *ctx) {
-    if (!ctx->vexp) return fail(ctx, PCL_EINVAL, "var_exp_hess = 1 needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)");
     const size_t need = var_exp_hess_lds_bytes(ctx, true, nullptr);
     // the plan: nine LDS tiles, or five and four in the workspace (var_exp_hess_tiles = 2: always; 1: where nine do not fit)
     const bool ws_plan = ctx->opt_vexph_tiles == 2 || (ctx->opt_vexph_tiles == 1 && need > (size_t)ctx->max_lds);
@@ -768,37 +767,6 @@ static int var_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, doub
     return PCL_OK;
 }
 
-// A large variational context (PCL_LARGE_N | PCL_LARGE_VAR, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is
-// refused in these words
-#define LARGE_VAR_NOTIMPL(ctx, what)                                                                                                   \
-    do {                                                                                                                               \
-        if ((ctx) && (ctx)->large_var)                                                                                                 \
-            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
-    } while (0)
-#define VAR_NOTIMPL(ctx, what)                                                                                                         \
-    do {                                                                                                                               \
-        LARGE_VAR_NOTIMPL(ctx, what);                                                                                                  \
-        if ((ctx) && (ctx)->var)                                                                                                       \
-            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (%s)", what, (ctx)->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL"); \
-    } while (0)
-// The compact Jacobian trio: refused in the same words unless the context's option var_compact is on.
-#define VAR_COMPACT_GATE(ctx, what)                                   \
-    do {                                                              \
-        if ((ctx) && (ctx)->var && !(ctx)->var_compact) VAR_NOTIMPL(ctx, what); \
-    } while (0)
-// The objective and the rollout: refused in the same words unless the context's option var_full is on (pcl_host_robust.hpp serves them then).
-#define VAR_GATE(ctx, what)                                        \
-    do {                                                           \
-        if ((ctx) && (ctx)->var && !(ctx)->var_full) VAR_NOTIMPL(ctx, what); \
-    } while (0)
-// The Hessian of the Lagrangian of PCL_BATCH_VARIATIONAL_EXP: its (u_i, u_j) block on component i needs third Frechet derivatives of exp.
-// Refused in these words unless the context's option var_exp_hess is on (var_exp_launch_hess serves it then).
-#define VAR_EXP_NOHESS(ctx, what)                                                                                                                                   \
-    do {                                                                                                                                                            \
-        if ((ctx) && (ctx)->vexp && !(ctx)->var_exp_hess)                                                                                                           \
-            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): the Hessian of the Lagrangian needs third Frechet derivatives of exp; solve with a quasi-Newton Hessian", what); \
-    } while (0)
-static int var_set_full(pcl_ctx *ctx, int64_t on);
 static int var_set_goal(pcl_ctx *ctx, const double *goal_iso_vec);
 static int var_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, const int32_t *subspace, int32_t ns);
 static int var_set_goal_form(pcl_ctx *ctx, int32_t scope, int32_t R, const double *A, const double *c);

@@ -22,6 +22,9 @@
 //   pcl_kernel_var_exp.hpp     the variational integrators on the exponential constraint (PCL_BATCH_VARIATIONAL_EXP): residual and Jacobian
 // and the host side beside this file in pcl_host_*.hpp, included in place: the launch ladders launch_fused (pcl_host_launch_pade.hpp) and launch_hess
 // (pcl_host_launch_hess.hpp) with one launcher per kernel family, on the helpers of pcl_host_launch.hpp; the large rollout's launcher stays in this file.
+// pcl_host_service.hpp has the kinds of context, the families of entry points and the one table of which kind serves which family under which option:
+// every entry point that a kind may refuse starts with require(ctx, family, its name), and the refusal sentences are stated there, once per kind.
+// pcl_host_options.hpp is pcl_set_option / pcl_get_option as one table of keys.
 // DESIGN.md has the full account.  No CPU fallback exists: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
@@ -333,6 +336,12 @@ static int fail(const pcl_ctx *ctx, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(ctx, PCL_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+#define TRY(expr)                 \
+    do {                          \
+        int rc_ = (expr);         \
+        if (rc_ != PCL_OK) return rc_; \
+    } while (0)
+
 // Every entry point runs on the context's device and leaves the caller's current device as it found it.
 namespace {
 struct DeviceGuard {
@@ -402,57 +411,8 @@ static int upload(pcl_ctx *ctx, T **dst, const std::vector<T> &src) {
 
 #include "pcl_host_jit.hpp"
 #include "pcl_host_launch.hpp"
+#include "pcl_host_service.hpp"
 #include "pcl_host_variational.hpp"
-
-// The exponential mode (PCL_ORDER_EXP) serves the residual, the Jacobian, the rollout and the objective family.  The compact Jacobian and the
-// merit / reduce payload are refused in these words unless the context's option exp_full is on, and so is the Hessian of the Lagrangian (its
-// (u_i, u_j) block needs second Frechet derivatives: pcl_kernel_exp_hess.hpp) unless its option exp_hess is.
-#define EXP_NOTIMPL(ctx, what)                                                                                                                      \
-    do {                                                                                                                                            \
-        if ((ctx) && (ctx)->exp) return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context of the exponential constraint (PCL_ORDER_EXP)", what); \
-    } while (0)
-
-// A large context (PCL_LARGE_N, generator dimensions 66 .. 128) serves the residual and the Jacobian; everything else is refused in these words
-// (the Hessian of the Lagrangian, the objective family and the rollout unless their options are on: the gates below).  A large exponential
-// context (PCL_LARGE_EXP) has the option large_full alone: its refusals name that flag.
-#define LARGE_NOTIMPL(ctx, what)                                                                                                                          \
-    do {                                                                                                                                                  \
-        if ((ctx) && (ctx)->large_exp)                                                                                                                    \
-            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large exponential context (PCL_LARGE_N | PCL_LARGE_EXP, generator dimension %d > 64): residual and Jacobian, and by option large_full the objective and the rollout", what, (ctx)->n); \
-        if ((ctx) && (ctx)->large)                                                                                                                        \
-            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, (ctx)->n); \
-        LARGE_VAR_NOTIMPL(ctx, what);                                                                                                                     \
-    } while (0)
-
-// ... its Hessian of the Lagrangian by option large_hess only (pcl_kernel_pade_large_hess.hpp; a large exponential context: by option large_exp_hess,
-// pcl_kernel_large_exp_hess.hpp): without it, the same words
-#define LARGE_HESS_GATE(ctx, what)                                \
-    do {                                                          \
-        if ((ctx) && !(ctx)->large_hess && !(ctx)->large_exp_hess) LARGE_NOTIMPL(ctx, what); \
-    } while (0)
-
-// ... and the objective family and the rollout by option large_full only (pcl_kernel_large_rollout.hpp): without it, the same words
-#define LARGE_FULL_GATE(ctx, what)                                \
-    do {                                                          \
-        if ((ctx) && !(ctx)->large_full) LARGE_NOTIMPL(ctx, what); \
-    } while (0)
-
-// ... and the compact Jacobian trio and the merit / reduce entry points by option large_reduce only (a large exponential context: by option
-// large_exp_reduce): without it, the same words
-#define LARGE_REDUCE_GATE(ctx, what)                                \
-    do {                                                            \
-        if ((ctx) && !(ctx)->large_reduce && !(ctx)->large_exp_reduce) LARGE_NOTIMPL(ctx, what); \
-    } while (0)
-
-#define EXP_HESS_GATE(ctx, what)                       \
-    do {                                               \
-        if ((ctx) && !(ctx)->exp_hess && !(ctx)->large_exp_hess) EXP_NOTIMPL(ctx, what); \
-    } while (0)
-// ... and the compact Jacobian trio and the merit / reduce entry points unless its option exp_full is on (a large exponential context: large_exp_reduce)
-#define EXP_FULL_GATE(ctx, what)                       \
-    do {                                               \
-        if ((ctx) && !(ctx)->exp_full && !(ctx)->large_exp_reduce) EXP_NOTIMPL(ctx, what); \
-    } while (0)
 
 extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (!out) return fail(nullptr, PCL_EINVAL, "pcl_create: out is NULL");
@@ -846,7 +806,7 @@ extern "C" int pcl_jac_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
 }
 extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count) {
     if (!ctx) return PCL_EINVAL;
-    VAR_NOTIMPL(ctx, "pcl_set_member_window");
+    TRY(require(ctx, FEAT_COLLECTIVE, "pcl_set_member_window"));
     if (first < 0 || count < 1 || (long long)first + count > ctx->desc.batch)
         return fail(ctx, PCL_EINVAL, "pcl_set_member_window: [%d, %d) outside the %d members of this context", first, first + count, ctx->desc.batch);
     ctx->win_first = first;
@@ -855,18 +815,14 @@ extern "C" int pcl_set_member_window(pcl_ctx *ctx, int32_t first, int32_t count)
 }
 extern "C" int pcl_jac_compact_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    LARGE_REDUCE_GATE(ctx, "pcl_jac_compact_nnz");
-    VAR_COMPACT_GATE(ctx, "pcl_jac_compact_nnz");
-    EXP_FULL_GATE(ctx, "pcl_jac_compact_nnz");
+    TRY(require(ctx, FEAT_COMPACT, "pcl_jac_compact_nnz"));
     if (per) *per = jac_per_compact(ctx);
     if (nnz) *nnz = jac_per_compact(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
 }
 extern "C" int pcl_hess_nnz(const pcl_ctx *ctx, int64_t *nnz, int64_t *per) {
     if (!ctx) return PCL_EINVAL;
-    LARGE_HESS_GATE(ctx, "pcl_hess_nnz");
-    VAR_EXP_NOHESS(ctx, "pcl_hess_nnz");
-    EXP_HESS_GATE(ctx, "pcl_hess_nnz");
+    TRY(require(ctx, FEAT_HESS, "pcl_hess_nnz"));
     if (per) *per = hess_per(ctx);
     if (nnz) *nnz = hess_per(ctx) * ctx->win_count * ctx->K;
     return PCL_OK;
@@ -935,9 +891,7 @@ template <class I>
 static int hess_structure_impl(const pcl_ctx *ctx, I *rows, I *cols) {
     if (!ctx) return PCL_EINVAL;
     if (!rows || !cols) return fail(ctx, PCL_EINVAL, "pcl_hess_structure: NULL output");
-    LARGE_HESS_GATE(ctx, "pcl_hess_structure");
-    VAR_EXP_NOHESS(ctx, "pcl_hess_structure");
-    EXP_HESS_GATE(ctx, "pcl_hess_structure");
+    TRY(require(ctx, FEAT_HESS, "pcl_hess_structure"));
     if (ctx->var) return var_hess_structure(ctx, rows, cols);
     const pcl_desc &D = ctx->desc;
     const long long m = D.n_drives, xd = ctx->x_dim, zd = D.z_dim, base = D.index_base;
@@ -1235,16 +1189,13 @@ extern "C" int pcl_jac_dev(pcl_ctx *ctx, const double *Z, double *vals) {  // ev
 extern "C" int pcl_eval_jac_compact_dev(pcl_ctx *ctx, const double *Z, double *delta, double *compact) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !compact) return fail(ctx, PCL_EINVAL, "pcl_eval_jac_compact_dev: NULL pointer");
-    LARGE_REDUCE_GATE(ctx, "pcl_eval_jac_compact_dev");
-    EXP_FULL_GATE(ctx, "pcl_eval_jac_compact_dev");
+    if (!ctx->var || ctx->large_var) TRY(require(ctx, FEAT_COMPACT, "pcl_eval_jac_compact_dev"));  // (a variational context of n <= 64: launch_fused refuses, as "the compact Jacobian")
     return launch_fused(ctx, Z, delta, compact, true);
 }
 extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!compact || !vals) return fail(ctx, PCL_EINVAL, "pcl_jac_expand_dev: NULL pointer");
-    LARGE_REDUCE_GATE(ctx, "pcl_jac_expand_dev");
-    VAR_COMPACT_GATE(ctx, "pcl_jac_expand_dev");
-    EXP_FULL_GATE(ctx, "pcl_jac_expand_dev");
+    TRY(require(ctx, FEAT_COMPACT, "pcl_jac_expand_dev"));
     ON_DEVICE(ctx);
     const long long n_bk = (long long)ctx->win_count * ctx->K;
     if (ctx->var) {  // every distinct tile to its cols copies in every segment it occurs in; at one column too (the tiles of component 0 repeat per variation)
@@ -1302,7 +1253,7 @@ extern "C" int pcl_jac_expand_dev(pcl_ctx *ctx, const double *compact, double *v
 extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess_dev: NULL pointer");
-    LARGE_HESS_GATE(ctx, "pcl_hess_dev");
+    if (ctx->large || ctx->large_var) TRY(require(ctx, FEAT_HESS, "pcl_hess_dev"));  // (every other kind: launch_hess refuses, as "pcl_hess")
     return launch_hess(ctx, Z, mu, vals);
 }
 
@@ -1380,8 +1331,7 @@ static int launch_large_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
 extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
-    LARGE_FULL_GATE(ctx, "pcl_rollout_dev");
-    VAR_GATE(ctx, "pcl_rollout_dev");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_rollout_dev"));
     if (ctx->var) return var_rollout_dev(ctx, Z, X_out);
     if (ctx->large) return launch_large_rollout(ctx, Z, X_out);
     ON_DEVICE(ctx);
@@ -1410,12 +1360,6 @@ static int ensure(pcl_ctx *ctx, double **buf, long long count) {
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "hipMalloc(%lld doubles): %s", count, hipGetErrorString(e));
     return PCL_OK;
 }
-#define TRY(expr)                 \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != PCL_OK) return rc_; \
-    } while (0)
-
 static int ensure_pinned(pcl_ctx *ctx, double **buf, long long count) {
     if (*buf) return PCL_OK;
     hipError_t e = hipHostMalloc((void **)buf, (size_t)count * sizeof(double), hipHostMallocDefault);
@@ -1456,10 +1400,8 @@ static int host_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double *v
     const auto t_begin = std::chrono::steady_clock::now();
     const long long nbk = (long long)ctx->win_count * ctx->K, nbk_all = (long long)(ctx->var ? 1 : ctx->desc.batch) * ctx->K;  // (variational: one stacked trajectory)
     const long long nv = jac_per_full(ctx) * nbk;
-    // (variational contexts without the option var_compact, and exponential ones without the option exp_full: full values, host_path 1)
-    // (large contexts: by the option large_reduce; large exponential ones: by the option large_exp_reduce)
-    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && (!ctx->large || ctx->large_reduce || ctx->large_exp_reduce) && (!ctx->var || ctx->var_compact) &&
-                              (!ctx->exp || ctx->exp_full || ctx->large_exp_reduce);
+    // (a context whose compact Jacobian is behind an option that is off: full values, as under host_path 1)
+    const bool compact_path = vals && ctx->cols > 1 && ctx->opt_host_path != 1 && serves(ctx, FEAT_COMPACT);
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
     TRY(ensure(ctx, &ctx->ddelta, n_rows_all(ctx)));
     TRY(ensure_pinned(ctx, &ctx->hZ, z_len(ctx)));
@@ -1552,9 +1494,7 @@ extern "C" int pcl_eval_jac(pcl_ctx *ctx, const double *Z, double *delta, double
 extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *vals) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !mu || !vals) return fail(ctx, PCL_EINVAL, "pcl_hess: NULL pointer");
-    LARGE_HESS_GATE(ctx, "pcl_hess");
-    VAR_EXP_NOHESS(ctx, "pcl_hess");
-    EXP_HESS_GATE(ctx, "pcl_hess");
+    TRY(require(ctx, FEAT_HESS, "pcl_hess"));
     ON_DEVICE(ctx);
     TRY(resolve_order(ctx, Z, "pcl_hess"));
     const long long nv = hess_per(ctx) * ctx->win_count * ctx->K;
@@ -1572,8 +1512,7 @@ extern "C" int pcl_hess(pcl_ctx *ctx, const double *Z, const double *mu, double 
 extern "C" int pcl_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout: NULL pointer");
-    LARGE_FULL_GATE(ctx, "pcl_rollout");
-    VAR_GATE(ctx, "pcl_rollout");
+    TRY(require(ctx, FEAT_OBJECTIVE, "pcl_rollout"));
     ON_DEVICE(ctx);
     const long long nv = (long long)ctx->win_count * ctx->desc.N * ctx->x_dim;
     TRY(ensure(ctx, &ctx->dZ, z_len(ctx)));
