@@ -15,6 +15,7 @@ All arithmetic happens on the GPU through the C ABI; nothing in this module
 computes a residual or a Jacobian on the host, and nothing falls back to a CPU
 implementation when the library or the device is missing.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -51,127 +52,132 @@ def _ptr(a):
     raise TypeError("unsupported buffer type %r" % type(a))
 
 
-def _exp_hessian_value(exp_hessian):
-    """The keyword ``exp_hessian``: ``False`` | ``True`` | ``"workspace"`` (anything else: ``ValueError``, before any device call)."""
-    if isinstance(exp_hessian, (bool, np.bool_)) or (isinstance(exp_hessian, (int, np.integer)) and exp_hessian in (0, 1)):
-        return bool(exp_hessian)
-    if isinstance(exp_hessian, str) and exp_hessian == "workspace":
-        return exp_hessian
-    raise ValueError("exp_hessian must be False, True or \"workspace\" (got %r)" % (exp_hessian,))
+# ---------------------------------------------------------------------------
+# The service keywords: what each means, stated once.  The constructors below name the ones they accept and point here.
+#
+# exp_hessian        ``False`` | ``True`` | ``"workspace"`` (anything else: ``ValueError``).  ``True``, with ``pade_order="exp"`` only: the Hessian of
+#                    the Lagrangian of the exponential constraint is served (second Frechet derivatives of exp; the library's option ``exp_hess``,
+#                    generator dimensions up to 62).  On a variational context the option is ``var_exp_hess`` (third Frechet derivatives, nine LDS
+#                    tiles: dimensions up to 44, beyond that the constructor raises the library's PCL_ESHAPE message); ``"workspace"`` sets
+#                    ``var_exp_hess_tiles`` = 1 first: where nine tiles exceed the LDS (dimensions 46 .. 62) four of them live in a device
+#                    workspace, elsewhere nothing changes.  ``"workspace"`` is the variational constructors' only.
+# exp_full           with ``pade_order="exp"`` on a plain context only: the compact Jacobian, the host-pointer calls' compact path and the merit /
+#                    reduce payload are served on that constraint too (option ``exp_full``).
+# var_compact        on a variational context only (any Pade order, or ``"exp"``): the compact Jacobian of the stacked state -- every distinct tile
+#                    once, ``ctx.compact_per`` values per interval -- its device expansion and the host-pointer calls' compact path.
+# large_generator    the flag ``PCL_LARGE_N``: generator dimensions 66 .. 128 (a transmon with a cavity, density vectors of 9 .. 11 levels) on the Pade
+#                    constraint, residual and Jacobian only -- the Hessian of the Lagrangian, the rollout, the objective, the compact Jacobian and
+#                    the payload raise the library's message unless the keywords below switch them on; solve with a quasi-Newton Hessian.  Without it
+#                    such a system is refused as before; at a dimension up to 64 it changes nothing and none of the large options is set (the
+#                    ordinary context serves everything as always).  With ``pade_order="exp"`` the library refuses it unless ``large_exp=True``.
+#                    On a variational constructor it sets ``PCL_LARGE_N | PCL_LARGE_VAR`` (``large_variational`` on the context): residual and
+#                    Jacobian of the Pade constraint, nothing else; with ``pade_order="exp"`` a ``ValueError``.
+# large_hessian      beside ``large_generator=True`` on the plain Pade constraint: the Hessian of the Lagrangian there (option ``large_hess``).
+# large_full         the same conditions, or beside ``large_exp=True``: the objective family -- goals, weights, regularisers, value, gradient, the
+#                    objective's Hessian -- and the rollout there (option ``large_full``): ``rollout``, ``rollout_dev``, ``Objective.bind`` work.
+# large_reduce       the same conditions as ``large_hessian``: the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``, ``eval_jac_compact_dev``,
+#                    ``jac_expand_dev``), the host-pointer calls' compact route and the merit / reduce payload (``merit_grad_dev``,
+#                    ``eval_jac_merit_dev`` -- with ``vals=None`` the payload alone -- and, with ``large_full``, ``eval_jac_merit_objective_dev``)
+#                    there (option ``large_reduce``).  The three are independent of each other.
+# large_exp          beside ``large_generator=True`` with ``pade_order="exp"`` on a plain context: the second flag ``PCL_LARGE_EXP``, the exponential
+#                    constraint at dimensions 66 .. 128, residual and exact Jacobian (a substepped Taylor polynomial, ``ceil(|dt| |G|_1)`` substeps:
+#                    the cost is linear in the step).  ``large_full`` is allowed beside it; ``large_hessian`` and ``large_reduce`` are not, and the
+#                    library refuses ``exp_hessian`` and ``exp_full`` there.  At a dimension up to 64 the ordinary exponential context serves.
+# large_exp_hessian  beside ``large_exp=True``: the Hessian of the Lagrangian of that constraint there (option ``large_exp_hess``: the adjoint of the
+#                    Jacobian's substepped recurrence with the second derivative carried; values, order and structure are ``exp_hessian``'s).  At
+#                    a dimension up to 64 it sets nothing (``exp_hessian`` is that context's switch).
+# large_exp_reduce   beside ``large_exp=True``: the compact Jacobian (layout ``[-E | tails]`` per interval), the host-pointer calls' compact route
+#                    and the merit / reduce payload there (option ``large_exp_reduce``).  At a dimension up to 64 it sets nothing (``exp_full``).
+#
+# All are off by default and none is ever switched on by itself.  One row of _SERVICES per rule: `when` -- the values of the keyword the row speaks
+# about ("on": any true one); what it sets -- a `flag` of pcl_desc.batch_mode or a library `option`; the keyword it stands `beside`; the `constraint`
+# it needs; the `family` of contexts it belongs to; the `sizes` on the context that follow its option (hess_nnz / hess_per, compact_nnz /
+# compact_per); `at`, the kind of context (an attribute of _PclContext) on which the constructor sets the option and set_option stores it, unless
+# the context is of the kind `yields`, which has a switch of its own; `refuse`, question -> sentence, in the order the questions are asked.
+# ROW ORDER IS PRECEDENCE: _check_services raises the first sentence that applies (tests/golden/keyword_trace.json has every combination).
+# ---------------------------------------------------------------------------
+_Service = collections.namedtuple("_Service", "keyword refuse when flag option beside constraint family sizes at yields", defaults=("on",) + (None,) * 8)
+_SERVICES = (
+    _Service("large_generator", {}, flag="PCL_LARGE_N"),
+    _Service("large_variational", flag="PCL_LARGE_VAR", beside="large_generator", constraint="pade context", family="variational", refuse={
+        "constraint": "large_generator=True on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" "
+                      "(PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts",
+        "family": "large_variational=True is the flag PCL_LARGE_VAR of a variational context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator with large_generator=True): a plain context takes large_generator=True alone",
+        "beside": "large_variational=True goes with large_generator=True (the flags PCL_LARGE_N | PCL_LARGE_VAR): it needs that keyword"}),
+    _Service("large_exp_hessian", option="large_exp_hess", beside="large_exp", family="plain", sizes="hess", at="large_exp", refuse={
+        "family": "large_exp_hessian=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)",
+        "beside": "large_exp_hessian=True is the Hessian of the Lagrangian of a context created with large_exp=True "
+                  "(large_generator=True, pade_order=\"exp\"): it needs that keyword"}),
+    _Service("large_exp_reduce", option="large_exp_reduce", beside="large_exp", family="plain", sizes="compact", at="large_exp", refuse={
+        "family": "large_exp_reduce=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)",
+        "beside": "large_exp_reduce=True is the compact Jacobian and the reduce payload of a context created with large_exp=True "
+                  "(large_generator=True, pade_order=\"exp\"): it needs that keyword"}),
+    _Service("large_exp", flag="PCL_LARGE_EXP", beside="large_generator", constraint="exp", family="plain", refuse={
+        "family": "large_exp=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)",
+        "beside": "large_exp=True is the exponential constraint of a context created with large_generator=True: it needs that keyword",
+        "constraint": "large_exp=True is the exponential constraint at generator dimensions 66 .. 128: it needs pade_order=\"exp\" (got %(order)r)"}),
+    _Service("large_hessian", option="large_hess", beside="large_generator", constraint="pade", family="plain", sizes="hess", at="large", refuse={
+        "family": "large_hessian=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint)",
+        "beside": "large_hessian=True is the Hessian of the Lagrangian of a context created with large_generator=True: it needs that keyword",
+        "constraint": "large_hessian=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts"}),
+    _Service("large_full", option="large_full", beside="large_generator", constraint="pade, or exp beside large_exp", family="plain", at="large", refuse={
+        "family": "large_full=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)",
+        "beside": "large_full=True is the objective and the rollout of a context created with large_generator=True: it needs that keyword",
+        "constraint": "large_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts"}),
+    _Service("large_reduce", option="large_reduce", beside="large_generator", constraint="pade", family="plain", sizes="compact", at="large", yields="large_exp", refuse={
+        "family": "large_reduce=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)",
+        "beside": "large_reduce=True is the compact Jacobian and the reduce payload of a context created with large_generator=True: it needs that keyword",
+        "constraint": "large_reduce=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts"}),
+    _Service("exp_hessian", when="any", refuse={"value": "exp_hessian must be False, True or \"workspace\" (got %(value)r)"}),
+    _Service("exp_full", option="exp_full", constraint="exp", family="plain", sizes="compact", at="exponential", yields="large_exp", refuse={
+        "constraint": "exp_full=True serves the compact Jacobian and the merit / reduce payload of the exponential constraint: it needs pade_order=\"exp\" (got %(order)r)",
+        "family": "exp_full=True is not served on a variational context"}),
+    _Service("var_compact", option="var_compact", family="variational", sizes="compact", at="variational", refuse={
+        "family": "var_compact=True serves the compact Jacobian of a variational context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator): a plain context has its compact Jacobian without it"}),
+    # (HipPadeIntegrator's own answer to "workspace", at any order: _PclContext answers it by the two rows below)
+    _Service("exp_hessian", when="workspace", family="no plain integrator", refuse={
+        "family": "exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint: a plain integrator takes False or True"}),
+    # (the option is exp_hess on a plain context, var_exp_hess on a variational one: _PclContext._key)
+    _Service("exp_hessian", option="exp_hess", constraint="exp", sizes="hess", at="exponential", refuse={
+        "constraint": "exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %(order)r)"}),
+    _Service("exp_hessian", when="workspace", option="var_exp_hess_tiles", family="variational exp", at="variational", refuse={
+        "family": "exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint (option var_exp_hess_tiles): "
+                  "it needs a variational context with pade_order=\"exp\""}),
+)
+_BY_OPTION = {row.option: row for row in _SERVICES if row.option}
+# the order in which a constructor switches the options on (the tile plan before the Hessian that reads it)
+_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "var_compact")
+_VARIATIONAL_MODES = (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
 
 
-def _check_exp_full(exp_full, pade_order, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``exp_full`` (the library's option of that name) belongs to a plain context of the exponential constraint: anything else is a
-    ``ValueError``, before any device call."""
-    if not exp_full:
-        return
-    if _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
-        raise ValueError("exp_full=True serves the compact Jacobian and the merit / reduce payload of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("exp_full=True is not served on a variational context")
-
-
-def _check_var_compact(var_compact, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``var_compact`` (the library's option of that name) belongs to a variational context, of either constraint kind: on any other
-    one it is a ``ValueError``, before any device call."""
-    if var_compact and batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("var_compact=True serves the compact Jacobian of a variational context (VariationalUnitaryIntegrator / "
-                         "VariationalKetIntegrator): a plain context has its compact Jacobian without it")
-
-
-def _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_hessian`` (the library's option ``large_hess``: the Hessian of the Lagrangian at generator dimensions 66 .. 128) goes with
-    ``large_generator=True`` on the Pade constraint of a plain context: anything else is a ``ValueError``, before any device call."""
-    if not large_hessian:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_hessian=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint)")
-    if not large_generator:
-        raise ValueError("large_hessian=True is the Hessian of the Lagrangian of a context created with large_generator=True: it needs that keyword")
-    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP:
-        raise ValueError("large_hessian=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
-
-
-def _check_large_full(large_full, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS, large_exp=False):
-    """The keyword ``large_full`` (the library's option of that name: the objective family and the rollout at generator dimensions 66 .. 128) goes
-    with ``large_generator=True`` on the Pade constraint of a plain context -- or on the exponential constraint beside ``large_exp=True``:
-    anything else is a ``ValueError``, before any device call."""
-    if not large_full:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_full=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_full is its option)")
-    if not large_generator:
-        raise ValueError("large_full=True is the objective and the rollout of a context created with large_generator=True: it needs that keyword")
-    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP and not large_exp:
-        raise ValueError("large_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
-
-
-def _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_reduce`` (the library's option of that name: the compact Jacobian, the host-pointer calls' compact route and the merit /
-    reduce payload at generator dimensions 66 .. 128) goes with ``large_generator=True`` on the Pade constraint of a plain context: anything else is
-    a ``ValueError``, before any device call."""
-    if not large_reduce:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_reduce=True is not served on a variational context (the flag PCL_LARGE_N goes with the plain Pade constraint; var_compact is its option)")
-    if not large_generator:
-        raise ValueError("large_reduce=True is the compact Jacobian and the reduce payload of a context created with large_generator=True: it needs that keyword")
-    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP:
-        raise ValueError("large_reduce=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" has no large contexts")
-
-
-def _check_large_exp(large_exp, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_exp`` (the library's flag ``PCL_LARGE_EXP``: the exponential constraint at generator dimensions 66 .. 128) goes with
-    ``large_generator=True`` and ``pade_order="exp"`` on a plain context: anything else is a ``ValueError``, before any device call."""
-    if not large_exp:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_exp=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)")
-    if not large_generator:
-        raise ValueError("large_exp=True is the exponential constraint of a context created with large_generator=True: it needs that keyword")
-    if _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
-        raise ValueError("large_exp=True is the exponential constraint at generator dimensions 66 .. 128: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
-
-
-def _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_exp_hessian`` (the library's option ``large_exp_hess``: the Hessian of the Lagrangian of the exponential constraint at
-    generator dimensions 66 .. 128) goes with ``large_exp=True`` -- and hence ``large_generator=True`` and ``pade_order="exp"`` -- on a plain
-    context: anything else is a ``ValueError``, before any device call."""
-    if not large_exp_hessian:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_exp_hessian=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)")
-    if not large_exp:
-        raise ValueError("large_exp_hessian=True is the Hessian of the Lagrangian of a context created with large_exp=True "
-                         "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
-
-
-def _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_exp_reduce`` (the library's option of that name: the compact Jacobian, the host-pointer calls' compact route and the
-    merit / reduce payload of the exponential constraint at generator dimensions 66 .. 128) goes with ``large_exp=True`` -- and hence
-    ``large_generator=True`` and ``pade_order="exp"`` -- on a plain context: anything else is a ``ValueError``, before any device call."""
-    if not large_exp_reduce:
-        return
-    if batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):
-        raise ValueError("large_exp_reduce=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)")
-    if not large_exp:
-        raise ValueError("large_exp_reduce=True is the compact Jacobian and the reduce payload of a context created with large_exp=True "
-                         "(large_generator=True, pade_order=\"exp\"): it needs that keyword")
-
-
-def _check_large_variational(large_variational, large_generator, pade_order, batch_mode=PCL_BATCH_MEMBERS):
-    """The keyword ``large_variational`` (the library's flag ``PCL_LARGE_VAR``: the variational integrators at generator dimensions 66 .. 128) goes
-    with ``large_generator=True`` on a variational context of the Pade constraint: anything else is a ``ValueError``, before any device call."""
-    if not large_variational:
-        return
-    if _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP or batch_mode == PCL_BATCH_VARIATIONAL_EXP:
-        raise ValueError("large_generator=True on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" "
-                         "(PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts")
-    if batch_mode != PCL_BATCH_VARIATIONAL:
-        raise ValueError("large_variational=True is the flag PCL_LARGE_VAR of a variational context (VariationalUnitaryIntegrator / "
-                         "VariationalKetIntegrator with large_generator=True): a plain context takes large_generator=True alone")
-    if not large_generator:
-        raise ValueError("large_variational=True goes with large_generator=True (the flags PCL_LARGE_N | PCL_LARGE_VAR): it needs that keyword")
+def _check_services(batch_mode=PCL_BATCH_MEMBERS, pade_order=4, *, plain_integrator=False, **keywords):
+    """Every service keyword against _SERVICES, before any device call: the first sentence that applies is a ``ValueError``.  ``keywords``: the
+    ones switched on (a missing one is off); ``plain_integrator``: the caller is HipPadeIntegrator.  Returns ``exp_hessian`` as ``False`` |
+    ``True`` | ``"workspace"``."""
+    variational = batch_mode in _VARIATIONAL_MODES
+    for row in _SERVICES:
+        value = keywords.get(row.keyword, False)
+        if (row.when == "on" and not value) or (row.when == "workspace" and not (isinstance(value, str) and value == "workspace")):
+            continue
+        for question, sentence in row.refuse.items():
+            if question == "value":
+                refused = not (isinstance(value, (bool, np.bool_)) or (isinstance(value, (int, np.integer)) and value in (0, 1))
+                               or (isinstance(value, str) and value == "workspace"))  # fmt: skip
+            elif question == "family":
+                refused = {"plain": variational, "variational": not variational, "variational exp": batch_mode != PCL_BATCH_VARIATIONAL_EXP,
+                           "no plain integrator": plain_integrator}[row.family]  # fmt: skip
+            elif question == "beside":
+                refused = not keywords.get(row.beside, False)
+            else:
+                exp = _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP
+                refused = {"exp": not exp, "pade": exp, "pade, or exp beside large_exp": exp and not keywords.get("large_exp", False),
+                           "pade context": exp or batch_mode == PCL_BATCH_VARIATIONAL_EXP}[row.constraint]  # fmt: skip
+            if refused:
+                raise ValueError(sentence % dict(order=pade_order, value=value))
+    value = keywords.get("exp_hessian", False)
+    return value if isinstance(value, str) else bool(value)
 
 
 class _PclContext:
@@ -181,22 +187,11 @@ class _PclContext:
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
                  large_exp_reduce=False, large_variational=False):  # fmt: skip
-        _check_large_variational(large_variational, large_generator, pade_order, batch_mode)
-        _check_large_exp_hessian(large_exp_hessian, large_exp, batch_mode)
-        _check_large_exp_reduce(large_exp_reduce, large_exp, batch_mode)
-        _check_large_exp(large_exp, large_generator, pade_order, batch_mode)
-        _check_large_hessian(large_hessian, large_generator, pade_order, batch_mode)
-        _check_large_full(large_full, large_generator, pade_order, batch_mode, large_exp)
-        _check_large_reduce(large_reduce, large_generator, pade_order, batch_mode)
+        keywords = dict(exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact, large_generator=large_generator, large_hessian=large_hessian,
+                        large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
+                        large_exp_reduce=large_exp_reduce, large_variational=large_variational)  # fmt: skip
+        keywords["exp_hessian"] = _check_services(batch_mode, pade_order, **keywords)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
-        exp_hessian = _exp_hessian_value(exp_hessian)
-        _check_exp_full(exp_full, pade_order, batch_mode)
-        _check_var_compact(var_compact, batch_mode)
-        if exp_hessian and pade_order != _lib.PCL_ORDER_EXP:
-            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
-        if exp_hessian == "workspace" and batch_mode != PCL_BATCH_VARIATIONAL_EXP:
-            raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint (option var_exp_hess_tiles): "
-                             "it needs a variational context with pade_order=\"exp\"")
         self._L = _lib.load()
         self._h = None
         n = d if state_cols == _lib.PCL_STATE_VECTOR else 2 * d  # PCL_STATE_VECTOR: general d x d generator, one column
@@ -227,64 +222,47 @@ class _PclContext:
         self.x_dim, self.n_rows, self.n_cols = a.value, b.value, c.value
         self._chk(self._L.pcl_jac_nnz(h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz, self.jac_per = a.value, b.value
-        # the exponential constraint: no compact Jacobian and no merit / reduce payload unless ``exp_full`` switches the library's option
-        # exp_full on, and no Hessian of the Lagrangian (hess_structure / hess raise with the library's message) unless ``exp_hessian``
-        # switches exp_hess on
+        # the kind of context (what each kind serves, and by which keyword: the table above).  The three flags change nothing at a generator
+        # dimension up to 64: the context is then an ordinary one of its constraint
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
-        self.exp_hessian = False  # (follows the library's option: set_option keeps it and hess_nnz / hess_per current)
-        self.exp_full = False  # (the same: set_option keeps it and compact_nnz / compact_per current)
-        self.var_compact = False  # (the same on a variational context, of either constraint kind)
-        self.hess_nnz = self.hess_per = 0
-        self.compact_nnz = self.compact_per = 0
-        # ``large_generator`` (the flag PCL_LARGE_N) at a generator dimension above 64: residual and Jacobian only -- the Hessian of the Lagrangian,
-        # the compact Jacobian, the merit / reduce payload, the rollout and the objective raise with the library's message (the rollout and the
-        # objective unless ``large_full`` switches the library's option of that name on).  At n <= 64 the
-        # flag changes nothing.  ``large_hessian`` switches the library's option large_hess on there: hess_nnz / hess_per follow it (set_option)
         self.large = bool(large_generator) and n > 64
-        # ``large_exp`` (the flag PCL_LARGE_EXP beside it, pade_order "exp"): residual and Jacobian of the exponential constraint there, the
-        # objective and the rollout by ``large_full``; the Hessian of the Lagrangian (unless ``large_exp_hessian``), the compact Jacobian and the
-        # payload (unless ``large_exp_reduce``) raise
         self.large_exp = bool(large_exp) and self.large
-        # ``large_variational`` (the flag PCL_LARGE_VAR beside it, a variational context of the Pade constraint): residual and Jacobian there; the
-        # Hessian of the Lagrangian, ``var_full`` (objective, rollout) and ``var_compact`` raise with the library's message
         self.large_variational = bool(large_variational) and self.large
-        self.large_exp_hessian = False  # (``large_exp_hessian`` switches the library's option large_exp_hess on there: hess_nnz / hess_per follow it, set_option)
-        self.large_exp_reduce = False  # (``large_exp_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
-        self.large_hessian = False
-        self.large_full = False  # (``large_full`` switches the library's option of that name on there: objective and rollout; set_option keeps it current)
-        self.large_reduce = False  # (``large_reduce`` switches the library's option of that name on there: compact Jacobian, merit / reduce payload; compact_nnz / compact_per follow it)
-        if exp_hessian == "workspace":  # (four of the nine tiles in a device workspace where nine exceed the LDS: generator dimensions 46 .. 62)
-            self.set_option("var_exp_hess_tiles", 1)
-        if exp_hessian:  # (a variational context of the constraint has an option of its own: third Frechet derivatives, nine LDS tiles)
-            self.set_option("var_exp_hess" if batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess", 1)
-        if large_hessian and self.large:  # (at n <= 64 the ordinary context serves its Hessian as always: the option is not set)
-            self.set_option("large_hess", 1)
-        elif large_exp_hessian and self.large_exp:  # (at n <= 64 ``exp_hessian`` is the ordinary exponential context's switch: the option is not set)
-            self.set_option("large_exp_hess", 1)
-        elif (self.exponential and not self.exp_hessian) or self.large:
-            self.hess_nnz = self.hess_per = 0
-        else:
-            self._chk(self._L.pcl_hess_nnz(h, ctypes.byref(a), ctypes.byref(b)))
-            self.hess_nnz, self.hess_per = a.value, b.value
-        if exp_full:
-            self.set_option("exp_full", 1)
-        if large_full and self.large:  # (at n <= 64 the ordinary context serves objective and rollout as always: the option is not set)
-            self.set_option("large_full", 1)
-        if large_reduce and self.large:  # (at n <= 64 the ordinary context serves them as always: the option is not set)
-            self.set_option("large_reduce", 1)
-        if large_exp_reduce and self.large_exp:  # (at n <= 64 ``exp_full`` is the ordinary exponential context's switch: the option is not set)
-            self.set_option("large_exp_reduce", 1)
-        if var_compact:
-            self.set_option("var_compact", 1)
-        # (the stacked state's compact Jacobian by ``var_compact`` only, the exponential constraint's by ``exp_full`` only: set_option has the sizes)
-        if batch_mode not in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP) and not self.exponential and not self.large:
-            self._chk(self._L.pcl_jac_compact_nnz(h, ctypes.byref(a), ctypes.byref(b)))
-            self.compact_nnz, self.compact_per = a.value, b.value
+        # a variational context: x_dim is the stacked state; goals and forms speak of component 0, the rollout returns one stacked trajectory
+        self.variational = batch_mode in _VARIATIONAL_MODES
+        # one attribute per option keyword, named like it: it follows the library's option (set_option), and so do the sizes the option governs
+        # (_refresh_sizes).  _switches: option key -> attribute, of the rows that apply to this kind of context
+        self._switches, self._governs = {}, {"hess": [], "compact": []}
+        for row in _BY_OPTION.values():
+            if row.when == "on":
+                setattr(self, row.keyword, False)
+                if getattr(self, row.at) and not (row.yields and getattr(self, row.yields)):
+                    self._switches[self._key(row)] = row.keyword
+                    if row.sizes:
+                        self._governs[row.sizes].append(row.keyword)
+        for option in _OPTION_ORDER:  # (a large option only on a large context: at n <= 64 the ordinary context serves as always, nothing is set)
+            row = _BY_OPTION[option]
+            value = keywords[row.keyword]
+            if (value == "workspace" if row.when == "workspace" else value) and getattr(self, row.at):
+                self.set_option(self._key(row), 1)
+        self._refresh_sizes()
         self.z_len = z_dim * N * (batch if batch_mode == PCL_BATCH_TRAJ else 1)
         self.window = (0, batch)
-        # a variational context: x_dim is the stacked state; goals and forms speak of component 0, the rollout returns one stacked trajectory
-        self.variational = batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
         self.goal_dim = self.x_dim // batch if self.variational else self.x_dim
+
+    def _key(self, row):
+        return "var_exp_hess" if row.option == "exp_hess" and self.batch_mode == PCL_BATCH_VARIATIONAL_EXP else row.option
+
+    def _refresh_sizes(self):
+        """hess_nnz / hess_per and compact_nnz / compact_per of the member window: current when no option of _SERVICES governs them on this kind
+        of context (a plain Pade context at n <= 64; the Hessian of a variational Pade one) or one that does is on; else 0."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        for sizes, count in (("hess", self._L.pcl_hess_nnz), ("compact", self._L.pcl_jac_compact_nnz)):
+            a.value = b.value = 0
+            if not self._governs[sizes] or any(getattr(self, keyword) for keyword in self._governs[sizes]):
+                self._chk(count(self._h, ctypes.byref(a), ctypes.byref(b)))
+            setattr(self, sizes + "_nnz", a.value)
+            setattr(self, sizes + "_per", b.value)
 
     def _chk(self, rc):
         if rc != 0:
@@ -425,26 +403,7 @@ class _PclContext:
         self.n_rows = b.value
         self._chk(self._L.pcl_jac_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
         self.jac_nnz = a.value
-        if self.exp_hessian:
-            self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.hess_nnz = a.value
-        if self.large:  # (the compact Jacobian by ``large_reduce`` only; the Hessian of the Lagrangian by ``large_hessian`` / ``large_exp_hessian`` only)
-            if self.large_hessian or self.large_exp_hessian:
-                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-                self.hess_nnz = a.value
-            if self.large_reduce or self.large_exp_reduce:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-                self.compact_nnz = a.value
-            return
-        if self.exponential:  # (the compact Jacobian by ``exp_full`` only, the Hessian of the Lagrangian by ``exp_hessian`` only)
-            if self.exp_full:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-                self.compact_nnz = a.value
-            return
-        self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-        self.hess_nnz = a.value
-        self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-        self.compact_nnz = a.value
+        self._refresh_sizes()
 
     # -- DerivativeIntegrator / time-consistency rows on this context's trajectory layout -----------------
     def deriv_dims(self, dx_off, dim):
@@ -596,51 +555,9 @@ class _PclContext:
 
     def set_option(self, key, value):
         self._chk(self._L.pcl_set_option(self._h, key.encode(), int(value)))
-        # the option that serves the Hessian of the Lagrangian of this context's exponential constraint: hess_nnz / hess_per follow it
-        if self.exponential and key == ("var_exp_hess" if self.batch_mode == PCL_BATCH_VARIATIONAL_EXP else "exp_hess"):
-            self.exp_hessian = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.exp_hessian:
-                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.hess_nnz, self.hess_per = a.value, b.value
-        if self.large and key == "large_hess":  # ... and the one that serves it on a large context
-            self.large_hessian = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.large_hessian:
-                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.hess_nnz, self.hess_per = a.value, b.value
-        if self.large_exp and key == "large_exp_hess":  # ... and on a large exponential context
-            self.large_exp_hessian = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.large_exp_hessian:
-                self._chk(self._L.pcl_hess_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.hess_nnz, self.hess_per = a.value, b.value
-        if self.large and key == "large_full":
-            self.large_full = bool(value)
-        if self.large and not self.large_exp and key == "large_reduce":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
-            self.large_reduce = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.large_reduce:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.compact_nnz, self.compact_per = a.value, b.value
-        if self.large_exp and key == "large_exp_reduce":  # ... and on a large exponential context
-            self.large_exp_reduce = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.large_exp_reduce:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.compact_nnz, self.compact_per = a.value, b.value
-        if key == "var_compact" and self.batch_mode in (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP):  # ... the stacked state's compact Jacobian
-            self.var_compact = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.var_compact:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.compact_nnz, self.compact_per = a.value, b.value
-        if self.exponential and not self.large_exp and key == "exp_full":  # ... and the one that serves its compact Jacobian: compact_nnz / compact_per follow it
-            self.exp_full = bool(value)
-            a, b = ctypes.c_int64(), ctypes.c_int64()
-            if self.exp_full:
-                self._chk(self._L.pcl_jac_compact_nnz(self._h, ctypes.byref(a), ctypes.byref(b)))
-            self.compact_nnz, self.compact_per = a.value, b.value
+        if key in self._switches:  # an option of _SERVICES that applies to this kind of context: its attribute and the sizes follow it
+            setattr(self, self._switches[key], bool(value))
+            self._refresh_sizes()
 
     def get_option(self, key):
         v = ctypes.c_int64()
@@ -706,52 +623,14 @@ class HipPadeIntegrator:
         (BASELINE.json's metric is quoted on 4, which deviates from the exp constraint by 1.6e-5 at config 3).  ``pade_order="exp"`` (or -1):
         the exponential constraint itself, ``x_{k+1} - exp(dt_k G(u_k)) x_k`` -- for steps too large for order 10 (``order_tol_met`` False); residual
         and Jacobian only: ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise, solve with a quasi-Newton Hessian.  Never chosen on its own.
-        ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served too
-        (second Frechet derivatives of exp; the library's option ``exp_hess``) -- generator dimensions up to 62.
-        ``exp_full=True`` (with ``pade_order="exp"`` only, else ``ValueError``): the compact Jacobian, the host-pointer calls' compact path and the
-        merit / reduce payload are served on that constraint too (the library's option ``exp_full``).
-        ``var_compact`` belongs to the variational constructors: ``True`` here is a ``ValueError``.
-        ``large_generator=True`` sets the library's flag ``PCL_LARGE_N``: generator dimensions 66 .. 128 (a transmon with a cavity, density vectors of
-        9 .. 11 levels) on the Pade constraint, residual and Jacobian only -- ``hessian_structure`` / ``eval_hessian_of_lagrangian``, the rollout and the
-        objective raise (see ``large_hessian`` and ``large_full`` below); solve with a quasi-Newton Hessian.  Never set on its own: without it such a system is refused as before.  With
-        ``pade_order="exp"`` the library refuses it unless ``large_exp=True`` is set as well (below).  At a dimension up to 64 it changes nothing.
-        ``large_hessian=True`` (with ``large_generator=True`` on the Pade constraint only, else ``ValueError``): the Hessian of the Lagrangian is served at
-        those dimensions too (the library's option ``large_hess``) -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work.  At a dimension up to
-        64 the ordinary context serves its Hessian as always.
-        ``large_full=True`` (the same conditions, else ``ValueError``): the objective family -- goals, weights, regularisers, value, gradient and the
-        objective's Hessian -- and the rollout are served at those dimensions too (the library's option ``large_full``): ``rollout``, ``rollout_dev``
-        and ``Objective.bind`` work unchanged.  Independent of ``large_hessian``; at a dimension up to 64 the ordinary context serves them as always.
-        ``large_reduce=True`` (the same conditions, else ``ValueError``): the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``, ``eval_jac_compact_dev``,
-        ``jac_expand_dev``), the host-pointer calls' compact route and the merit / reduce payload (``merit_grad_dev``, ``eval_jac_merit_dev`` -- with
-        ``vals=None`` the payload alone -- and, together with ``large_full``, ``eval_jac_merit_objective_dev``) are served at those dimensions too (the
-        library's option ``large_reduce``).  Independent of the other two; at a dimension up to 64 the ordinary context serves them as always.
-        ``large_exp=True`` (with ``large_generator=True`` and ``pade_order="exp"`` only, else ``ValueError``) sets the library's second flag
-        ``PCL_LARGE_EXP``: the exponential constraint at generator dimensions 66 .. 128, residual and exact Jacobian (a substepped Taylor polynomial,
-        ``ceil(|dt| |G|_1)`` substeps: the cost is linear in the step).  ``large_full=True`` is allowed beside it (objective and rollout);
-        ``large_hessian``, ``large_reduce``, ``exp_hessian`` and ``exp_full`` are not: solve with a quasi-Newton Hessian, or set ``large_exp_hessian`` (below).  Never set on its own;
-        at a dimension up to 64 the ordinary exponential context serves the constraint as always.
-        ``large_exp_hessian=True`` (with ``large_exp=True`` only, else ``ValueError``): the Hessian of the Lagrangian of that constraint is served at
-        those dimensions too (the library's option ``large_exp_hess``: the adjoint of the Jacobian's substepped recurrence with the second
-        derivative carried; values, order and structure are those of ``exp_hessian``) -- ``hessian_structure`` and
-        ``eval_hessian_of_lagrangian`` work.  Off by default and never on by itself; at a dimension up to 64 it sets nothing (``exp_hessian`` is
-        that context's switch).
-        ``large_exp_reduce=True`` (with ``large_exp=True`` only, else ``ValueError``): the compact Jacobian (``ctx.compact_nnz`` / ``compact_per``,
-        ``eval_jac_compact_dev``, ``jac_expand_dev``, layout ``[-E | tails]`` per interval), the host-pointer calls' compact route and the merit /
-        reduce payload (``merit_grad_len``, ``merit_grad_dev``, ``eval_jac_merit_dev``, also with ``vals=None``) are served there too (the library's
-        option ``large_exp_reduce``).  Off by default and never on by itself; at a dimension up to 64 it sets nothing (``exp_full`` is that context's switch)."""
-        _check_large_exp_hessian(large_exp_hessian, large_exp)
-        _check_large_exp_reduce(large_exp_reduce, large_exp)
-        _check_large_exp(large_exp, large_generator, pade_order)
-        _check_large_hessian(large_hessian, large_generator, pade_order)
-        _check_large_full(large_full, large_generator, pade_order, PCL_BATCH_MEMBERS, large_exp)
-        _check_large_reduce(large_reduce, large_generator, pade_order)
-        exp_hessian = _exp_hessian_value(exp_hessian)
-        _check_exp_full(exp_full, pade_order)
-        _check_var_compact(var_compact)
-        if exp_hessian == "workspace":
-            raise ValueError("exp_hessian=\"workspace\" is the tile plan of the variational exponential constraint: a plain integrator takes False or True")
-        if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
-            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
+
+        The service keywords ``exp_hessian`` (``False`` or ``True`` here), ``exp_full``, ``large_generator``, ``large_hessian``, ``large_full``,
+        ``large_reduce``, ``large_exp``, ``large_exp_hessian`` and ``large_exp_reduce``: what each serves and what it must stand beside is said
+        once, above ``_SERVICES`` in this module; a combination the table refuses is a ``ValueError`` before any device call.  ``var_compact``
+        belongs to the variational constructors: ``True`` here is a ``ValueError``."""
+        exp_hessian = _check_services(PCL_BATCH_MEMBERS, pade_order, plain_integrator=True, exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact,
+                                      large_generator=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
+                                      large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce)  # fmt: skip
         x_names = [x_name] if isinstance(x_name, str) else list(x_name)
         G_drives = np.asarray(G_drives, dtype=np.float64)
         G_drift = np.asarray(G_drift, dtype=np.float64)
@@ -842,34 +721,20 @@ class HipVariationalIntegrator:
     ``pade_order="exp"`` (or -1): the reference's own constraint ``x'_{k+1} = exp(dt_k var_G(..)) x'_k`` instead of a Pade discretisation of
     it -- a context of batch_mode PCL_BATCH_VARIATIONAL_EXP, for the steps whose lifted ``theta`` no Pade order follows.  Residual, Jacobian,
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
-    derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian=True`` (with ``pade_order="exp"`` only, else ``ValueError``) switches
-    the library's option ``var_exp_hess`` on: the Hessian of the Lagrangian of that constraint is then served too, for generator dimensions up
-    to 44 (nine LDS tiles; beyond that the constructor raises the library's PCL_ESHAPE message).  ``exp_hessian="workspace"`` sets the option
-    ``var_exp_hess_tiles`` = 1 first: where nine tiles exceed the LDS (generator dimensions 46 .. 62, config 3 among them) four of them live in
-    a device workspace, elsewhere nothing changes.  Any other value is a ``ValueError``.  It is never on by itself.
+    derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian`` switches them on.
 
-    ``var_compact=True`` (any Pade order, or ``"exp"``) switches the library's option ``var_compact`` on: the compact Jacobian of the stacked
-    state -- every distinct tile once, ``ctx.compact_per`` values per interval -- its device expansion, and the host-pointer calls' compact
-    path (compact values over PCIe, replicated by the host's threads) are served.  Off by default and never on by itself.
-
-    ``large_generator=True`` sets the library's flags ``PCL_LARGE_N | PCL_LARGE_VAR``: generator dimensions 66 .. 128 (a transmon with a cavity)
-    on the Pade constraint -- residual and Jacobian; ``hessian_structure`` / ``eval_hessian_of_lagrangian``, ``rollout`` and
-    ``enable_objective_and_rollout`` raise the library's message there (solve with a quasi-Newton Hessian).  At 64 and below it changes nothing.
-    With ``pade_order="exp"`` it is a ``ValueError``; never on by itself."""
+    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact`` and ``large_generator``: what each serves is
+    said once, above ``_SERVICES`` in this module.  The other large keywords are accepted and, switched on, refused in the table's words."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
                  large_exp_hessian=False, large_exp_reduce=False):
-        _check_large_variational(large_generator, large_generator, pade_order, PCL_BATCH_VARIATIONAL)
-        _check_large_exp_hessian(large_exp_hessian, large_exp, PCL_BATCH_VARIATIONAL)
-        _check_large_exp_reduce(large_exp_reduce, large_exp, PCL_BATCH_VARIATIONAL)
-        _check_large_exp(large_exp, False, pade_order, PCL_BATCH_VARIATIONAL)
-        _check_large_hessian(large_hessian, False, pade_order, PCL_BATCH_VARIATIONAL)
-        _check_large_full(large_full, False, pade_order, PCL_BATCH_VARIATIONAL)
-        _check_large_reduce(large_reduce, False, pade_order, PCL_BATCH_VARIATIONAL)
-        exp_hessian = _exp_hessian_value(exp_hessian)
-        if exp_hessian and _lib.order_code(pade_order) != _lib.PCL_ORDER_EXP:
-            raise ValueError("exp_hessian=True is the Hessian of the Lagrangian of the exponential constraint: it needs pade_order=\"exp\" (got %r)" % (pade_order,))
+        pade_order = _lib.order_code(pade_order)
+        self.exponential = pade_order == _lib.PCL_ORDER_EXP
+        batch_mode = PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL
+        exp_hessian = _check_services(batch_mode, pade_order, exp_hessian=exp_hessian, var_compact=var_compact, large_generator=large_generator,
+                                      large_variational=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
+                                      large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce)  # fmt: skip
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -895,12 +760,10 @@ class HipVariationalIntegrator:
         self.G_drives = np.asarray(sys.G_drives_array(), dtype=np.float64).reshape(m, n, n)
         self.G_vars = np.asarray(Gv, dtype=np.float64).reshape(len(Gv), n, n)
         self._sig = (traj.dim, traj.N)
-        pade_order = _lib.order_code(pade_order)
-        self.exponential = pade_order == _lib.PCL_ORDER_EXP
         self._ctx = _PclContext(
             d=sys.levels, m=m, N=traj.N, z_dim=traj.dim, u_off=traj.components[u_name].start, dt_off=traj.components[traj.timestep].start,
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
-            batch=len(names), batch_mode=PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL, per_member_G0=True, global_dim=traj.global_dim, device=device,
+            batch=len(names), batch_mode=batch_mode, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
             large_generator=bool(large_generator), large_variational=bool(large_generator),
         )  # fmt: skip
@@ -1215,10 +1078,7 @@ def BilinearIntegrator(system, traj, x_name=None, u_name="u", **kw):
     their drive generators too (each member uses its full ``sys.G`` [REF integrators.jl:149-162]) gets one context per
     member.
 
-    The keywords are ``HipPadeIntegrator``'s.  Among them ``large_generator=True, large_exp=True`` with ``pade_order="exp"`` is the exponential
-    constraint at generator dimensions 66 .. 128 (residual and Jacobian), and ``large_exp_hessian=True`` beside them serves its Hessian of the
-    Lagrangian as well -- ``hessian_structure`` and ``eval_hessian_of_lagrangian`` work; without ``large_exp=True`` it is a ``ValueError``.
-    ``large_exp_reduce=True`` beside ``large_exp=True`` serves the compact Jacobian and the merit / reduce payload there (a ``ValueError`` without it)."""
+    The keywords are ``HipPadeIntegrator``'s (the service keywords among them: above ``_SERVICES`` in this module)."""
     if isinstance(system, (list, tuple)):
         from .quantum import OpenQuantumSystem
         from .trajectory import DENSITY

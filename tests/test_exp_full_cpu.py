@@ -59,9 +59,9 @@ def test_exp_full_keyword_needs_the_exponential_constraint():
     for mode in (pa._lib.PCL_BATCH_VARIATIONAL, pa._lib.PCL_BATCH_VARIATIONAL_EXP):
         with pytest.raises(ValueError, match="variational"):
             pa.integrators._PclContext(pade_order="exp", exp_full=True, **dict(args, batch_mode=mode))
-    pa.integrators._check_exp_full(True, "exp")
-    pa.integrators._check_exp_full(True, -1)
-    pa.integrators._check_exp_full(False, 4)
+    pa.integrators._check_services(pade_order="exp", exp_full=True)
+    pa.integrators._check_services(pade_order=-1, exp_full=True)
+    pa.integrators._check_services(pade_order=4, exp_full=False)
 
 
 def test_jacobian_views_with_the_exponential_offsets():

@@ -194,9 +194,9 @@ def test_mirror_value_errors():
     with pytest.raises(ValueError, match="has no large contexts"):
         P(**_kw(large_generator=True, large_full=True))
     with pytest.raises(ValueError, match="has no large contexts"):
-        pa.integrators._check_large_full(True, True, "exp", pa._lib.PCL_BATCH_MEMBERS)
-    pa.integrators._check_large_full(True, True, "exp", pa._lib.PCL_BATCH_MEMBERS, True)  # ... and beside it: allowed
-    pa.integrators._check_large_full(True, True, "exp", large_exp=True)
+        pa.integrators._check_services(pa._lib.PCL_BATCH_MEMBERS, "exp", large_full=True, large_generator=True)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_MEMBERS, "exp", large_full=True, large_generator=True, large_exp=True)  # ... and beside it: allowed
+    pa.integrators._check_services(pade_order="exp", large_full=True, large_generator=True, large_exp=True)
 
 
 def test_mirror_keyword_reaches_the_library():

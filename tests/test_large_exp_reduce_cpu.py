@@ -139,5 +139,5 @@ def test_keyword_value_errors_come_before_any_device_call():
         pa.integrators.HipVariationalIntegrator(None, None, "x", ["v"], "u", None, ket=True, large_exp_reduce=True)
     with pytest.raises(ValueError, match="large_exp=True"):
         pa.HipPadeIntegrator(np.zeros((4, 4)), np.zeros((1, 4, 4)), None, large_exp_reduce=True)
-    pa.integrators._check_large_exp_reduce(False, False, pa._lib.PCL_BATCH_VARIATIONAL)  # off: nothing to check
-    pa.integrators._check_large_exp_reduce(True, True)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_VARIATIONAL, large_exp_reduce=False, large_exp=False)  # off: nothing to check
+    pa.integrators._check_services(pa._lib.PCL_BATCH_MEMBERS, "exp", large_exp_reduce=True, large_exp=True, large_generator=True)  # (large_exp=True: with what it stands beside)

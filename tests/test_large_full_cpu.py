@@ -95,7 +95,7 @@ def test_keyword_errors_without_a_device():
         pa.HipPadeIntegrator(np.zeros((66, 66)), np.zeros((1, 66, 66)), None, pade_order="exp", large_generator=True, large_full=True)
     with pytest.raises(ValueError, match="variational"):
         pi.HipVariationalIntegrator(None, None, "x", ["v"], "u", [None], ket=True, large_full=True)
-    pi._check_large_full(False, False, "exp", pi.PCL_BATCH_VARIATIONAL)  # (off: nothing to check)
+    pi._check_services(pi.PCL_BATCH_VARIATIONAL, "exp", large_full=False, large_generator=False)  # (off: nothing to check)
 
 
 def test_objective_cases_sit_on_both_sides_of_the_kink():

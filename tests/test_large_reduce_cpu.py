@@ -142,5 +142,5 @@ def test_keyword_value_errors_come_before_any_device_call():
         pa.integrators.HipVariationalIntegrator(None, None, "x", ["v"], "u", None, ket=True, large_reduce=True)
     with pytest.raises(ValueError, match="large_generator=True"):
         pa.HipPadeIntegrator(np.zeros((4, 4)), np.zeros((1, 4, 4)), None, large_reduce=True)
-    pa.integrators._check_large_reduce(False, False, "exp", pa._lib.PCL_BATCH_VARIATIONAL)  # off: nothing to check
-    pa.integrators._check_large_reduce(True, True, 8)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_VARIATIONAL, "exp", large_reduce=False, large_generator=False)  # off: nothing to check
+    pa.integrators._check_services(pade_order=8, large_reduce=True, large_generator=True)

@@ -141,9 +141,9 @@ def test_var_compact_keyword_needs_a_variational_context():
     with pytest.raises(ValueError, match="var_compact"):
         pa.integrators._PclContext(pade_order=4, var_compact=True, batch_mode=pa._lib.PCL_BATCH_TRAJ, **args)
     for mode in (pa._lib.PCL_BATCH_VARIATIONAL, pa._lib.PCL_BATCH_VARIATIONAL_EXP):
-        pa.integrators._check_var_compact(True, mode)
-    pa.integrators._check_var_compact(False)
-    pa.integrators._check_var_compact(0, pa._lib.PCL_BATCH_TRAJ)
+        pa.integrators._check_services(mode, var_compact=True)
+    pa.integrators._check_services(var_compact=False)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_TRAJ, var_compact=0)
 
 
 def test_host_expanders_in_a_standalone_program(tmp_path):

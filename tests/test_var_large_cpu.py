@@ -276,9 +276,9 @@ def test_mirror_keywords():
         for lg in (False, True):
             with pytest.raises(ValueError, match="variational"):
                 V(None, None, "x", ["v"], "u", [None], ket=True, large_generator=lg, **{other: True})
-    pa.integrators._check_large_variational(False, False, "exp", pa._lib.PCL_BATCH_MEMBERS)  # off: nothing to check
-    pa.integrators._check_large_variational(True, True, 8, pa._lib.PCL_BATCH_VARIATIONAL)
-    pa.integrators._check_large_variational(True, True, 0, pa._lib.PCL_BATCH_VARIATIONAL)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_MEMBERS, "exp", large_variational=False, large_generator=False)  # off: nothing to check
+    pa.integrators._check_services(pa._lib.PCL_BATCH_VARIATIONAL, 8, large_variational=True, large_generator=True)
+    pa.integrators._check_services(pa._lib.PCL_BATCH_VARIATIONAL, 0, large_variational=True, large_generator=True)
 
 
 def test_mirror_never_sets_the_flags_by_itself():
