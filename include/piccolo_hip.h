@@ -322,7 +322,16 @@ typedef enum pcl_status {
  * their kind.
  * Options: "cols_per_slice" caps the state columns per chain workgroup, "general_slices" sets the least number of panel workgroups per role,
  * "var_large_drives" caps the drives per group (0 auto; PCL_EINVAL when negative or off such a context); "var_block_wgs" / "var_col_wgs" have
- * no effect.  get_option "last_kernel" reads 340 + q after a residual + Jacobian launch and 350 + q after a residual-only launch. */
+ * no effect.  get_option "last_kernel" reads 340 + q after a residual + Jacobian launch and 350 + q after a residual-only launch.
+ * Option "large_var_full" (0 by default, never on by itself; 1 on every other kind of context, and any other value, PCL_EINVAL; readable
+ * everywhere, 0 there): at 1 such a context serves pcl_set_goal, pcl_set_goal_subspace, pcl_set_goal_form (scope 0), pcl_set_weights,
+ * pcl_add_regularizer, pcl_clear_regularizers, pcl_objective[_dev], pcl_objective_hess_nnz / _structure, pcl_objective_hess[_dev] and
+ * pcl_rollout[_dev] with the contracts, layouts and value order of "var_full" at n <= 64: the robust-control objective and the rollout of the
+ * stacked state x <- E x, x_i <- E x_i + L_i x, output [N][(1 + v) n C] (pcl_kernel_var_large_rollout.hpp; "last_kernel"
+ * 360).  Back at 0 the refusals return in the same words and goal, weights and regularisers are dropped.  "var_full" = 1 stays PCL_ENOTIMPL
+ * naming PCL_LARGE_VAR at either value, and so do the Hessian of the Lagrangian, the compact trio, the merit / reduce entry points, the
+ * member window and pcl_infidelity_dev.  A subspace goal of more than 45 levels is PCL_ESHAPE (2 ns^2 + 2 rows of the form against 4096);
+ * a failed device allocation (a triangle of the objective's Hessian is 268 MB at d = 64) is PCL_ENOMEM and the context goes on as before. */
 #define PCL_LARGE_VAR 0x400
 
 typedef struct pcl_desc {

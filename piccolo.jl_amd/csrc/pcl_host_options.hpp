@@ -127,6 +127,7 @@ static const OptRow kOptions[] = {
     gate_row("large_exp_reduce", GATE_LARGE_EXP_REDUCE),
     gate_row("large_full", GATE_LARGE_FULL),    // (0: also drops goal, weights, regularisers)
     gate_row("large_reduce", GATE_LARGE_REDUCE),
+    gate_row("large_var_full", GATE_LARGE_VAR_FULL),  // (0: also drops goal, weights, regularisers)
     // ... the most drives per group of the large launches (0 auto), and the rollout's stages for measurements (0 both launches | 1 the propagators only | 2 the chain only)
     opt_row("var_large_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_var_large_drives, 0, OPT_MAX, 0, 0,
             "%s must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)", &pcl_ctx::large_var),

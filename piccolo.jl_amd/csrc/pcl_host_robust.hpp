@@ -29,6 +29,25 @@ static int var_set_full(pcl_ctx *ctx, int64_t on) {
     ctx->var_full = (int)on;
     return PCL_OK;
 }
+// a device array of this family whose allocation may fail for its size (a triangle at d = 64 is 268 MB): PCL_ENOMEM, the pointer stays NULL, the
+// sticky HIP error is cleared and the context goes on as before
+static int var_alloc(pcl_ctx *ctx, void **buf, size_t bytes, const char *what) {
+    const hipError_t e = hipMalloc(buf, bytes);
+    if (e == hipSuccess) return PCL_OK;
+    *buf = nullptr;
+    (void)hipGetLastError();
+    return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "%s (%zu B): %s", what, bytes, hipGetErrorString(e));
+}
+// option large_var_full (large variational contexts): what var_set_full does for var_full
+static int var_large_set_full(pcl_ctx *ctx, int64_t on) {
+    if ((int)on == ctx->large_var_full) return PCL_OK;  // (set_gate has checked the value and the kind of context)
+    ON_DEVICE(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (on && !ctx->dvar_coef) TRY(var_alloc(ctx, (void **)&ctx->dvar_coef, (size_t)(ctx->var + 1) * sizeof(double), "large_var_full = 1: the coefficient buffer"));
+    var_drop_objective(ctx);
+    ctx->large_var_full = (int)on;
+    return PCL_OK;
+}
 static bool var_unitary(const pcl_ctx *ctx) { return ctx->cols == ctx->desc.d; }
 static bool var_has_goal(const pcl_ctx *ctx) { return ctx->dformA || ctx->dformc; }
 static bool var_has_sens(const pcl_ctx *ctx) {
@@ -53,6 +72,10 @@ static int var_set_goal_subspace(pcl_ctx *ctx, const double *goal_sub_iso_vec, c
         for (int j = 0; j < i; ++j)
             if (subspace[j] == subspace[i]) return fail(ctx, PCL_EINVAL, "pcl_set_goal_subspace: index %d repeated", subspace[i]);
     }
+    // (a large variational context, d up to 64: the size no subspace of d <= 32 reaches; refused here, before anything is replaced.  No kernel of
+    // this path stages the subspace in LDS, so the rows of the form are the only limit)
+    if (ctx->large_var && 2 * ns * ns + 2 > PCL_FORM_MAX_ROWS)
+        return fail(ctx, PCL_ESHAPE, "pcl_set_goal_subspace: a subspace of %d levels needs %d rows of the terminal form (2 ns^2 + 2), %d are available: 45 levels at most", ns, 2 * ns * ns + 2, PCL_FORM_MAX_ROWS);
     ON_DEVICE(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return subspace_form(ctx, goal_sub_iso_vec, subspace, ns);
@@ -209,8 +232,10 @@ static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
             if (*q) (void)hipFree(*q);
             *q = nullptr;
         }
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dvar_last_src, std::max<size_t>(P.last_src.size(), 1) * sizeof(int)));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->dvar_diag, P.diag.size() * sizeof(double)));
+        ctx->var_last_src.clear();
+        ctx->var_diag.clear();
+        TRY(var_alloc(ctx, (void **)&ctx->dvar_last_src, std::max<size_t>(P.last_src.size(), 1) * sizeof(int), "pcl_objective_hess_dev: the kept slots of the terminal knot"));
+        TRY(var_alloc(ctx, (void **)&ctx->dvar_diag, P.diag.size() * sizeof(double), "pcl_objective_hess_dev: the absorbed diagonals"));
         HIP_TRY(ctx, hipMemcpy(ctx->dvar_last_src, P.last_src.data(), P.last_src.size() * sizeof(int), hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(ctx->dvar_diag, P.diag.data(), P.diag.size() * sizeof(double), hipMemcpyHostToDevice));
         ctx->var_last_src = P.last_src;
@@ -230,7 +255,7 @@ static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
         if (b == 0) {
             if (!ctx->gram_ready) {  // T = 2 sum_r A_r A_r', once per goal
                 const PclForm f{ctx->dformA, ctx->dformc, ctx->form_R, (int)L, 0};
-                if (!ctx->dgram) HIP_TRY(ctx, hipMalloc((void **)&ctx->dgram, (size_t)nT * sizeof(double)));
+                if (!ctx->dgram) TRY(var_alloc(ctx, (void **)&ctx->dgram, (size_t)nT * sizeof(double), "pcl_objective_hess_dev: the Gram triangle"));
                 hipLaunchKernelGGL(pcl_gram_kernel, dim3((unsigned)std::min<long long>((nT + 255) / 256, 4096)), dim3(256), 0, ctx->stream, f, ctx->dgram);
                 HIP_TRY(ctx, hipGetLastError());
                 ctx->gram_ready = true;
@@ -240,6 +265,9 @@ static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
         } else {
             const double c = sigma * ctx->var_w[b] / ((double)D.d * D.d);
             const long long pairs = (nT + 1) / 2;
+            // (the staged x is L doubles: 65,536 B at d = 64, where a launch has to ask for its dynamic LDS)
+            if ((size_t)L * sizeof(double) >= 65536)
+                HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_sens_hess_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)L * sizeof(double))));
             hipLaunchKernelGGL(pcl_sens_hess_kernel, dim3((unsigned)std::min<long long>((pairs + 255) / 256, 2048)), dim3(256), (size_t)L * sizeof(double), ctx->stream,
                                zN + ctx->x_offs[b], (const double *)(ctx->dvar_coef + b), c, (int)L, out);
         }
@@ -280,6 +308,89 @@ static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
 }
 
 // --- rollout of the stacked state (pcl_kernel_var_rollout.hpp) -----------------------------------------------------------------------------
+// The same on a large variational context (pcl_kernel_var_large_rollout.hpp; option large_var_full).  Beside the tile (LD = n | 1) a propagator
+// workgroup holds three pairs [V | Vv] of npc columns: six blocks; a chain workgroup holds two pairs [X | Xv] of nc state columns and no tile.
+// The widest panel that fits is evened over the panels; launches of few intervals take up to one panel per 16 columns while the grid of
+// (1 + v) roles stays within one round of the CUs (option general_slices: that many panels per role at least).  The chain takes slices of 16
+// state columns, one matrix-core column tile (option cols_per_slice: that many at most, never more than 16).  One column always fits
+// (n = 128, m = 24: 139,568 B and 5,152 B).  Every split gives the same bits.
+struct VarLargeRollPlan {
+    int LD, threads, P, npc, S, nc;
+    size_t lds_e, lds_c;
+};
+static void var_large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, long long K, VarLargeRollPlan &R) {
+    R.LD = n | 1;
+    R.threads = 64 * ((n + 15) / 16);
+    const long long budget = ctx->max_lds / (long long)sizeof(double), tile = (long long)R.LD * n;
+    const long long fixed_e = tile + PL_SLACK + m + 8, fixed_c = PL_SLACK;
+    const int npc_max = (int)std::max<long long>(1, std::min<long long>(n, (budget - fixed_e) / R.LD / 6));
+    const int p_min = (n + npc_max - 1) / npc_max;
+    const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices : std::min<long long>((n + 15) / 16, ctx->n_cu / std::max(K * (1 + v), 1LL));
+    R.P = (int)std::max<long long>(p_min, std::min<long long>(want, n));
+    R.npc = (n + R.P - 1) / R.P;
+    R.P = (n + R.npc - 1) / R.npc;  // (no panel without a column)
+    const int nc_fit = (int)std::max<long long>(1, (budget - fixed_c) / R.LD / 4);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
+    R.nc = std::min(std::min(nc_cap, nc_fit), 16);
+    R.S = (cols + R.nc - 1) / R.nc;
+    R.lds_e = (size_t)(fixed_e + 6LL * R.LD * R.npc) * sizeof(double);
+    R.lds_c = (size_t)(fixed_c + 4LL * R.LD * R.nc) * sizeof(double);
+}
+static int var_large_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
+    ON_DEVICE(ctx);
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, v = ctx->var, m = D.n_drives;
+    const size_t ws = (size_t)ctx->K * (1 + v) * n * n * sizeof(double);  // [interval][E | L_1 .. L_v], kept until pcl_destroy
+    if (!ctx->dexpm) TRY(var_alloc(ctx, (void **)&ctx->dexpm, ws, "pcl_rollout_dev: the propagator workspace"));
+    VarLargeRollPlan R;
+    var_large_roll_plan(ctx, n, ctx->cols, m, v, ctx->K, R);
+    if (R.lds_e > (size_t)ctx->max_lds || R.lds_c > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "pcl_rollout_dev: the large variational rollout needs %zu B of LDS (> %d) for n = %d, m = %d", std::max(R.lds_e, R.lds_c), ctx->max_lds, n, m);
+    const long long grid_e = (long long)ctx->K * (1 + v) * R.P, grid_c = (long long)v * R.S;
+    if (grid_e > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_rollout_dev: %lld workgroups exceed the grid limit", grid_e);
+    KParams p;
+    memset(&p, 0, sizeof p);
+    p.Z = Z;
+    p.xout = X_out;
+    p.expm = ctx->dexpm;
+    p.G0 = ctx->dvar_tab;  // (build_G as var_large_launch sets it up: the drift, and the drives on the union table)
+    p.upos = ctx->dupos;
+    p.ucoef = ctx->ducoef;
+    p.n_upos = ctx->n_upos;
+    p.x_off0 = -1;
+    p.d = D.d;
+    p.n = n;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.batch = 1;
+    p.cols = ctx->cols;
+    p.LD = R.LD;
+    VarLargeRollParams w;
+    memset(&w, 0, sizeof w);
+    w.gv_val = ctx->dvl_gval;
+    w.gv_col = ctx->dvl_gcol;
+    w.gv_w = ctx->vl_gw;
+    w.v = v;
+    for (int b = 0; b <= v; ++b) w.xo[b] = ctx->x_offs[b];
+    w.npc = R.npc;
+    w.P = R.P;
+    w.nc = R.nc;
+    w.S = R.S;
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_var_large_expm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.lds_e));
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)pcl_var_large_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R.lds_c));
+    p.lds_doubles = (int)(R.lds_e / sizeof(double));
+    hipLaunchKernelGGL(pcl_var_large_expm_kernel, dim3((unsigned)grid_e), dim3((unsigned)R.threads), R.lds_e, ctx->stream, p, w);
+    HIP_TRY(ctx, hipGetLastError());
+    p.lds_doubles = (int)(R.lds_c / sizeof(double));
+    hipLaunchKernelGGL(pcl_var_large_chain_kernel, dim3((unsigned)grid_c), dim3((unsigned)R.threads), R.lds_c, ctx->stream, p, w);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_kernel = 360;  // the large variational family's rollout (340 + q: residual + Jacobian, 350 + q: its residual)
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
 static int var_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     ON_DEVICE(ctx);
     const pcl_desc &D = ctx->desc;

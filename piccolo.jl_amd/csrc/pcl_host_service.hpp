@@ -23,7 +23,7 @@ enum Feature {
 
 // The gate options (OPTIONS.md): a context flag each, 0 by default.
 enum Gate { GATE_NONE, GATE_EXP_HESS, GATE_EXP_FULL, GATE_VAR_FULL, GATE_VAR_COMPACT, GATE_VAR_EXP_HESS, GATE_LARGE_HESS, GATE_LARGE_FULL, GATE_LARGE_REDUCE,
-            GATE_LARGE_EXP_HESS, GATE_LARGE_EXP_REDUCE, N_GATES };
+            GATE_LARGE_EXP_HESS, GATE_LARGE_EXP_REDUCE, GATE_LARGE_VAR_FULL, N_GATES };
 
 static int exp_hess_fits(const pcl_ctx *ctx, const char *who);
 static int var_exp_hess_enable(pcl_ctx *ctx);
@@ -31,6 +31,7 @@ static int large_hess_enable(pcl_ctx *ctx);
 static int large_exp_hess_enable(pcl_ctx *ctx);
 static int var_set_full(pcl_ctx *ctx, int64_t on);
 static int large_set_full(pcl_ctx *ctx, int64_t on);
+static int var_large_set_full(pcl_ctx *ctx, int64_t on);
 
 #define KIND_BIT(k) (1u << (k))
 struct GateInfo {
@@ -59,6 +60,8 @@ static const GateInfo kGates[N_GATES] = {
      [](pcl_ctx *c, int64_t on) { return on ? large_exp_hess_enable(c) : PCL_OK; }},
     {&pcl_ctx::large_exp_reduce, 0, "%s = 1 needs a large exponential context (batch_mode | PCL_LARGE_N | PCL_LARGE_EXP, pade_order = PCL_ORDER_EXP, at a generator dimension above 64); every other context serves its compact Jacobian and reduce payload without it or by an option of its own", FEAT_COMPACT,
      nullptr},
+    {&pcl_ctx::large_var_full, 0, "%s = 1 needs a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64); every other context serves its objective and rollout without it or by an option of its own", FEAT_OBJECTIVE,
+     var_large_set_full},
 };
 
 // One cell of the table: served always ({}), never (NEVER), or while every gate it names is on.  `words` replaces the kind's refusal sentence.
@@ -79,7 +82,7 @@ static const Cell kService[N_KINDS][N_FEATURES] = {
     /* VAR_EXP   */ {{GATE_VAR_EXP_HESS, GATE_NONE, false, kVarExpHessWords}, {GATE_VAR_FULL}, NEVER,   {GATE_VAR_COMPACT},      NEVER,                   NEVER,                                    NEVER},
     /* LARGE     */ {{GATE_LARGE_HESS},                         {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE, GATE_LARGE_FULL},     ALWAYS},
     /* LARGE_EXP */ {{GATE_LARGE_EXP_HESS},                     {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE, GATE_LARGE_FULL}, ALWAYS},
-    /* LARGE_VAR */ {NEVER,                                     NEVER,              NEVER,              NEVER,                   NEVER,                   NEVER,                                    NEVER},
+    /* LARGE_VAR */ {NEVER,                                     {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
 };
 
 static bool serves(const pcl_ctx *ctx, Feature f) {

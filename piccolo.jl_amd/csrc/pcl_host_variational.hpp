@@ -8,6 +8,7 @@
 #include "pcl_kernel_var_exp_hess.hpp"
 #include "pcl_kernel_var_exp_hess_tiles.hpp"
 #include "pcl_kernel_var_large.hpp"
+#include "pcl_kernel_var_large_rollout.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
@@ -776,3 +777,4 @@ static int var_objective_hess_nnz(const pcl_ctx *ctx, int64_t *nnz);
 static int var_objective_hess_structure(const pcl_ctx *ctx, int64_t *rows, int64_t *cols);
 static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, double sigma, double *vals);
 static int var_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out);
+static int var_large_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out);

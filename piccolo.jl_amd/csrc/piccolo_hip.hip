@@ -8,6 +8,7 @@
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
 //   pcl_kernel_large_exp_hess.hpp   ... its Hessian of the Lagrangian (option large_exp_hess): the adjoint of that recurrence with the second derivative carried, per-column partial sums
 //   pcl_kernel_var_large.hpp        ... the variational integrators there (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR): chain units of 1 + v components, panel units of the powers and, one variation at a time, the Frechet powers
+//   pcl_kernel_var_large_rollout.hpp ... ... their rollout of the stacked state (option large_var_full): E and the Frechet derivatives L_i by column panels of one substepped Horner recurrence, then the chain of the knots
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
@@ -116,6 +117,7 @@ struct pcl_ctx {
     long long var_off_d = 0, var_voff_d = 0, var_off_v = 0, var_voff_v = 0;
     int64_t opt_var_blocks = 0, opt_var_cols = 0;  // ... block / column workgroups per interval of the fused launch (0 auto)
     int large_var = 0;                    // ... PCL_LARGE_N | PCL_LARGE_VAR with 66 <= n <= 128: every residual / Jacobian launch is pcl_var_large_kernel (pcl_kernel_var_large.hpp); everything else is refused; its tables are dupos / ducoef / dell_* (the drives, as a plain large context has them) and the two below
+    int large_var_full = 0;               // ... ... option large_var_full: the robust-control objective family and the rollout of the stacked state are served (pcl_host_robust.hpp, pcl_kernel_var_large_rollout.hpp; its workspace is dexpm)
     int64_t opt_var_large_drives = 0;     // ... ... the most drives per group of that launch (0 auto: all of them where they fit)
     int *dvl_gcol = nullptr;              // ... ... the variation generators row-compressed, [v][n][vl_gw] (row-major, zero padded)
     double *dvl_gval = nullptr;
@@ -1332,6 +1334,7 @@ extern "C" int pcl_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {
     if (!ctx) return PCL_EINVAL;
     if (!Z || !X_out) return fail(ctx, PCL_EINVAL, "pcl_rollout_dev: NULL pointer");
     TRY(require(ctx, FEAT_OBJECTIVE, "pcl_rollout_dev"));
+    if (ctx->large_var) return var_large_rollout_dev(ctx, Z, X_out);
     if (ctx->var) return var_rollout_dev(ctx, Z, X_out);
     if (ctx->large) return launch_large_rollout(ctx, Z, X_out);
     ON_DEVICE(ctx);

@@ -71,7 +71,12 @@ def _ptr(a):
 #                    such a system is refused as before; at a dimension up to 64 it changes nothing and none of the large options is set (the
 #                    ordinary context serves everything as always).  With ``pade_order="exp"`` the library refuses it unless ``large_exp=True``.
 #                    On a variational constructor it sets ``PCL_LARGE_N | PCL_LARGE_VAR`` (``large_variational`` on the context): residual and
-#                    Jacobian of the Pade constraint, nothing else; with ``pade_order="exp"`` a ``ValueError``.
+#                    Jacobian of the Pade constraint, nothing else unless ``large_var_full`` is on; with ``pade_order="exp"`` a ``ValueError``.
+# large_var_full     beside ``large_generator=True`` on a variational constructor (Pade constraint): the robust-control objective family -- goals,
+#                    weights, regularisers, value, gradient, the objective's Hessian -- and the rollout of the stacked state at dimensions
+#                    66 .. 128 (option ``large_var_full``): ``Objective.bind``, ``rollout``, ``rollout_dev``, ``variational_rollout`` work.  The
+#                    Hessian of the Lagrangian and the compact Jacobian stay refused there.  At a dimension up to 64 it sets nothing (``var_full``,
+#                    which ``enable_objective_and_rollout`` switches on, is that context's option).
 # large_hessian      beside ``large_generator=True`` on the plain Pade constraint: the Hessian of the Lagrangian there (option ``large_hess``).
 # large_full         the same conditions, or beside ``large_exp=True``: the objective family -- goals, weights, regularisers, value, gradient, the
 #                    objective's Hessian -- and the rollout there (option ``large_full``): ``rollout``, ``rollout_dev``, ``Objective.bind`` work.
@@ -105,6 +110,11 @@ _SERVICES = (
         "family": "large_variational=True is the flag PCL_LARGE_VAR of a variational context (VariationalUnitaryIntegrator / "
                   "VariationalKetIntegrator with large_generator=True): a plain context takes large_generator=True alone",
         "beside": "large_variational=True goes with large_generator=True (the flags PCL_LARGE_N | PCL_LARGE_VAR): it needs that keyword"}),
+    _Service("large_var_full", option="large_var_full", beside="large_generator", constraint="pade context", family="variational", at="large_variational", refuse={
+        "family": "large_var_full=True is the objective and the rollout of a large variational context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator with large_generator=True): a plain context takes large_full=True",
+        "beside": "large_var_full=True is the objective and the rollout of a variational context created with large_generator=True: it needs that keyword",
+        "constraint": "large_var_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"}),
     _Service("large_exp_hessian", option="large_exp_hess", beside="large_exp", family="plain", sizes="hess", at="large_exp", refuse={
         "family": "large_exp_hessian=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)",
         "beside": "large_exp_hessian=True is the Hessian of the Lagrangian of a context created with large_exp=True "
@@ -148,7 +158,7 @@ _SERVICES = (
 )
 _BY_OPTION = {row.option: row for row in _SERVICES if row.option}
 # the order in which a constructor switches the options on (the tile plan before the Hessian that reads it)
-_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "var_compact")
+_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "large_var_full", "var_compact")
 _VARIATIONAL_MODES = (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
 
 
@@ -186,10 +196,10 @@ class _PclContext:
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False, large_variational=False):  # fmt: skip
+                 large_exp_reduce=False, large_variational=False, large_var_full=False):  # fmt: skip
         keywords = dict(exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact, large_generator=large_generator, large_hessian=large_hessian,
                         large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
-                        large_exp_reduce=large_exp_reduce, large_variational=large_variational)  # fmt: skip
+                        large_exp_reduce=large_exp_reduce, large_variational=large_variational, large_var_full=large_var_full)  # fmt: skip
         keywords["exp_hessian"] = _check_services(batch_mode, pade_order, **keywords)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         self._L = _lib.load()
@@ -723,18 +733,19 @@ class HipVariationalIntegrator:
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
     derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian`` switches them on.
 
-    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact`` and ``large_generator``: what each serves is
+    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator`` and ``large_var_full``: what each serves is
     said once, above ``_SERVICES`` in this module.  The other large keywords are accepted and, switched on, refused in the table's words."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
-                 large_exp_hessian=False, large_exp_reduce=False):
+                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False):
         pade_order = _lib.order_code(pade_order)
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         batch_mode = PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL
         exp_hessian = _check_services(batch_mode, pade_order, exp_hessian=exp_hessian, var_compact=var_compact, large_generator=large_generator,
                                       large_variational=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
-                                      large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce)  # fmt: skip
+                                      large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce,
+                                      large_var_full=large_var_full)  # fmt: skip
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -765,7 +776,7 @@ class HipVariationalIntegrator:
             x_offs=[traj.components[nm].start for nm in names], G0=np.concatenate([self.G_drift[None], self.G_vars]), Gj=self.G_drives,
             batch=len(names), batch_mode=batch_mode, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
-            large_generator=bool(large_generator), large_variational=bool(large_generator),
+            large_generator=bool(large_generator), large_variational=bool(large_generator), large_var_full=bool(large_var_full),
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)
@@ -789,7 +800,10 @@ class HipVariationalIntegrator:
 
     def enable_objective_and_rollout(self):
         """Switch the context's ``var_full`` option on: the objective entry points and the rollout then serve it (a freshly built integrator
-        refuses them).  ``Objective.bind``, ``rollout`` and ``variational_rollout`` call this themselves."""
+        refuses them).  ``Objective.bind``, ``rollout`` and ``variational_rollout`` call this themselves.  A large variational context whose
+        ``large_var_full`` is on serves them already: nothing is done there."""
+        if self._ctx.large_variational and self._ctx.large_var_full:
+            return
         if not self._ctx.get_option("var_full"):
             self._ctx.set_option("var_full", 1)
 

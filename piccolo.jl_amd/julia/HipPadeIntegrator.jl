@@ -230,7 +230,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
-const PCL_LARGE_VAR = 1024  # (0x400) a third batch_mode flag beside PCL_LARGE_N (keyword large_generator of the variational integrators): PCL_BATCH_VARIATIONAL on the Pade constraint at generator dimensions 66 .. 128: residual and Jacobian
+const PCL_LARGE_VAR = 1024  # (0x400) a third batch_mode flag beside PCL_LARGE_N (keyword large_generator of the variational integrators): PCL_BATCH_VARIATIONAL on the Pade constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout of the stacked state with large_var_full = true
 const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true, compact Jacobian and reduce payload with large_exp_reduce = true
 _order_code(p::Integer) = Int(p)
 _order_code(p::Symbol) = p === :exp ? PCL_ORDER_EXP : error("HipPadeIntegrator: pade_order = :$p (a diagonal Pade order, 0 or :exp)")
@@ -330,12 +330,16 @@ end
 #      off by default, never on by itself.
 #      large_generator = true: the library's flags PCL_LARGE_N | PCL_LARGE_VAR in batch_mode -- generator dimensions 66 .. 128 on the Pade
 #      constraint: residual and Jacobian; no Hessian of the Lagrangian (the structure stays empty, solve with eval_hessian = false), no
-#      objective or rollout from the library.  With pade_order = :exp: ArgumentError.  At 64 and below it changes nothing; never on by itself.
+#      objective or rollout from the library unless large_var_full = true.  With pade_order = :exp: ArgumentError.  At 64 and below it
+#      changes nothing; never on by itself.
+#      large_var_full = true (with large_generator = true on the Pade constraint only): the library's option large_var_full -- the
+#      robust-control objective family and the rollout of the stacked state at generator dimensions 66 .. 128; _enable_var_full! then does
+#      nothing there (without the keyword it raises the library's message naming PCL_LARGE_VAR, as before).  At 64 and below it sets nothing.
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
                       var_compact::Bool = false, large_generator::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false,
-                      large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false)
+                      large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false, large_var_full::Bool = false)
     large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
@@ -346,6 +350,10 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     expo = pade_order == PCL_ORDER_EXP
     (large_generator && expo) &&
         throw(ArgumentError("HipPadeIntegrator: large_generator = true on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large variational contexts"))
+    (large_var_full && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_full = true is the objective and the rollout of a variational context created with large_generator = true: it needs that keyword"))
+    (large_var_full && expo) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_full = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"))
     (exp_hessian isa Symbol && exp_hessian != :workspace) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian must be false, true or :workspace (got :$(exp_hessian))"))
     workspace = exp_hessian === :workspace
@@ -378,6 +386,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
     var_compact && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_compact", 1))
     large_var = large_generator && size(G0, 1) > 64                   # (a large variational context: the Hessian of the Lagrangian is refused)
+    (large_var && large_var_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_full", 1))
     ((expo && !exp_hessian) || large_var) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
@@ -406,6 +415,9 @@ _is_variational(B::HipPadeIntegrator) = length(getfield(B, :x_names)) > 1 && _co
 function _enable_var_full!(B::HipPadeIntegrator)
     _is_variational(B) || error("a variational integrator (VariationalUnitaryIntegrator / VariationalKetIntegrator) is required")
     c = _core(B).ctx
+    lvf = Ref{Int64}(0)   # a large variational context with large_var_full on serves the objective and the rollout already
+    check(c, ccall((:pcl_get_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Ref{Int64}), c, "large_var_full", lvf))
+    lvf[] == 1 && return c
     check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_full", 1))
     return c
 end
