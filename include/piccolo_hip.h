@@ -145,7 +145,8 @@ typedef enum pcl_status {
                                PCL_ESHAPE), evolved by the lifted generator var_G(G(u), [Gv_i]) = [[G, 0..], [Gv_1, G, 0..], .., [Gv_v, 0.., G]]
                                per state column.  batch = 1 + v; x_offs[0] the state, x_offs[i] variation i; per_member_G0 = 1 with
                                G0[0] = G_drift and G0[i] = Gv_i = G(H_var_i) / scale_i (the caller applies the scales); state_cols d
-                               (unitary) or 1 (ket), not PCL_STATE_VECTOR.
+                               (unitary) or 1 (ket), not PCL_STATE_VECTOR (with PCL_LARGE_N | PCL_LARGE_VAR at d > 32 also any count of
+                               kets between: see PCL_LARGE_VAR).
                                x_dim (pcl_constraint_dim) is the stacked (1 + v) n C.  Rows are KNOT-major over the stacked state,
                                row k*x_dim + b*(n C) + c*n + i (component b, state column c) -- the reference's B.dim = x_dim (N-1) -- and
                                NOT the member-major order of PCL_BATCH_MEMBERS.  Jacobian values per interval (pcl_jac_structure):
@@ -304,8 +305,9 @@ typedef enum pcl_status {
  *   PCL_LARGE_VAR without PCL_LARGE_N, or with PCL_BATCH_MEMBERS / PCL_BATCH_TRAJ           PCL_EINVAL
  *   PCL_LARGE_VAR with PCL_BATCH_VARIATIONAL_EXP or with PCL_LARGE_EXP                      PCL_ENOTIMPL naming PCL_LARGE_VAR
  *   PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, n <= 64                            the ordinary variational context: same kernels, same bits
- *   the same, 66 <= n <= 128 (n = 2d is even), v = 1 or 2, m <= 24, state_cols d or 1,
- *     pade_order 0 / 2 / 4 / 6 / 8 / 10                                                     a LARGE VARIATIONAL context
+ *   the same, 66 <= n <= 128 (n = 2d is even), v = 1 or 2, m <= 24, state_cols d, 1 or any
+ *     count of kets between (the kernels are planned per slice of state columns; at n <= 64
+ *     a count between stays PCL_EINVAL), pade_order 0 / 2 / 4 / 6 / 8 / 10                  a LARGE VARIATIONAL context
  *   the same, n > 128                                                                       PCL_ESHAPE with the byte counts, as for PCL_LARGE_N
  * -- all decided before the device is touched.  Such a context runs one kernel (pcl_kernel_var_large.hpp, on the one-tile plan of the large
  * family: chain workgroups per (interval, slice of state columns, drive group) carry W, V and the dW_l of all 1 + v components, panel workgroups

@@ -26,8 +26,11 @@ static int var_validate(const pcl_desc *D, bool large_var) {
         return fail(nullptr, PCL_EINVAL, "pcl_create: per_member_G0=%d; PCL_BATCH_VARIATIONAL takes per_member_G0 = 1 (G0[0] = G_drift, G0[i] = Gv_i)", D->per_member_G0);
     if (D->state_cols == PCL_STATE_VECTOR) return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=PCL_STATE_VECTOR is not supported by PCL_BATCH_VARIATIONAL");
     if (d < 1) return fail(nullptr, PCL_EINVAL, "pcl_create: d=%d", d);
-    if (D->state_cols != 0 && D->state_cols != 1 && D->state_cols != d)
-        return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=%d; PCL_BATCH_VARIATIONAL takes d (unitary, or 0) or 1 (ket)", D->state_cols);
+    // a large variational context also takes 2 .. d - 1 kets: its one kernel and its rollout are planned per slice of state columns, whatever their count
+    const bool kets = large_var && d > PCL_MAX_D && D->state_cols > 1 && D->state_cols < d;
+    if (D->state_cols != 0 && D->state_cols != 1 && D->state_cols != d && !kets)
+        return fail(nullptr, PCL_EINVAL, "pcl_create: state_cols=%d; PCL_BATCH_VARIATIONAL takes d (unitary, or 0) or 1 (ket), and with PCL_LARGE_N | PCL_LARGE_VAR at d > %d any count of kets up to d",
+                    D->state_cols, PCL_MAX_D);
     if (m < 0) return fail(nullptr, PCL_EINVAL, "pcl_create: n_drives=%d", m);
     if (D->N < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: N=%d; need N >= 2", D->N);
     if (D->batch_mode == PCL_BATCH_VARIATIONAL_EXP) {
