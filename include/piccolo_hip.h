@@ -331,9 +331,18 @@ typedef enum pcl_status {
  * pcl_rollout[_dev] with the contracts, layouts and value order of "var_full" at n <= 64: the robust-control objective and the rollout of the
  * stacked state x <- E x, x_i <- E x_i + L_i x, output [N][(1 + v) n C] (pcl_kernel_var_large_rollout.hpp; "last_kernel"
  * 360).  Back at 0 the refusals return in the same words and goal, weights and regularisers are dropped.  "var_full" = 1 stays PCL_ENOTIMPL
- * naming PCL_LARGE_VAR at either value, and so do the Hessian of the Lagrangian, the compact trio, the merit / reduce entry points, the
+ * naming PCL_LARGE_VAR at either value, and so do the Hessian of the Lagrangian (its option is "large_var_hess", below), the compact trio, the merit / reduce entry points, the
  * member window and pcl_infidelity_dev.  A subspace goal of more than 45 levels is PCL_ESHAPE (2 ns^2 + 2 rows of the form against 4096);
- * a failed device allocation (a triangle of the objective's Hessian is 268 MB at d = 64) is PCL_ENOMEM and the context goes on as before. */
+ * a failed device allocation (a triangle of the objective's Hessian is 268 MB at d = 64) is PCL_ENOMEM and the context goes on as before.
+ * Option "large_var_hess" (0 by default, never on by itself; 1 on every other kind of context, and any other value, PCL_EINVAL; readable
+ * everywhere, 0 there): at 1 such a context serves pcl_hess_nnz, pcl_hess_structure[_i64], pcl_hess and pcl_hess_dev with the values, order and
+ * structure of PCL_BATCH_VARIATIONAL at n <= 64 for the same pcl_desc: (m + 1)(m + 2) / 2 + 2 x_dim' (m + 1) values per interval over the
+ * stacked state (pcl_kernel_var_large_hess.hpp: the chains of the large Hessian kernel on the lifted generator, one pass per component;
+ * DESIGN.md 4.28; "last_hess_kernel" 340 + q).  Back at 0 the refusals return in the same words.  Its workspace is allocated when the option
+ * is first set to 1 (PCL_ENOMEM when that fails) and freed by pcl_destroy.  "large_var_hess_drives" caps the drives per workgroup of that
+ * launch (0 auto; PCL_EINVAL when negative or off such a context), "cols_per_slice" its state columns; every split gives the same bits.  With
+ * multipliers that are zero on the variations, the scalars and the vectors of component 0 have the bits of a plain PCL_LARGE_N context with
+ * "large_hess" on the same drift and drives.  The other refusals above stay at either value. */
 #define PCL_LARGE_VAR 0x400
 
 typedef struct pcl_desc {

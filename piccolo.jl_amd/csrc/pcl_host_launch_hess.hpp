@@ -76,6 +76,161 @@ static int launch_pade_large_hess(pcl_ctx *ctx, const double *Z, const double *m
     return PCL_OK;
 }
 
+// Hessian of the Lagrangian of a large variational context (pcl_kernel_var_large_hess.hpp; option large_var_hess).  The plan is large_hess_plan's
+// with twice the column blocks -- a unit holds component 0 and the component of the running pass: nc (20 + 8 mg) blocks of LD doubles beside the
+// tile -- and the same partial sums: the widest nc that leaves room for one drive (option cols_per_slice caps it), then the most drives per group
+// that fit (option large_var_hess_drives caps them), slices and groups evened.  One column and one drive always fit (n = 128, m = 24: 162,480 B).
+// Every split gives the same bits.
+static size_t var_large_hess_lds_bytes(int n, int m, int nc, int mg) {
+    const size_t LD = (size_t)(n | 1);
+    return (LD * n + LD * nc * (20 + 8 * (size_t)mg) + PL_SLACK + m + 8 + (size_t)nc * ((size_t)mg * (m + 1) + 1)) * sizeof(double);
+}
+static void var_large_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeHessPlan &P) {
+    P.LD = n | 1;
+    P.threads = 64 * ((n + 15) / 16);
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
+    const int mg_cap = m > 0 ? (ctx->opt_large_var_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_var_hess_drives, m) : m) : 0;
+    const int mg_min = m > 0 ? 1 : 0;
+    P.nc = 1;
+    for (int nc = nc_cap; nc > 1; --nc)
+        if (var_large_hess_lds_bytes(n, m, nc, mg_min) <= (size_t)ctx->max_lds) {
+            P.nc = nc;
+            break;
+        }
+    P.mg = mg_min;
+    for (int mg = mg_cap; mg > mg_min; --mg)
+        if (var_large_hess_lds_bytes(n, m, P.nc, mg) <= (size_t)ctx->max_lds) {
+            P.mg = mg;
+            break;
+        }
+    P.ngrp = m > 0 ? (m + P.mg - 1) / P.mg : 1;
+    if (m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
+    P.sx = (cols + P.nc - 1) / P.nc;
+    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.U = P.sx * P.ngrp;
+    P.lds = var_large_hess_lds_bytes(n, m, P.nc, P.mg);
+}
+// option large_var_hess = 1: the workspace of the partial sums and the transposed row tables of the drives and of the variation generators
+// (allocated here, on first use, not by pcl_create; the tables come from the lifted host copies the order policy keeps)
+static int var_large_hess_alloc(pcl_ctx *ctx, void **buf, size_t bytes, const char *what) {
+    const hipError_t e = hipMalloc(buf, std::max<size_t>(bytes, 8));
+    if (e == hipSuccess) return PCL_OK;
+    *buf = nullptr;
+    (void)hipGetLastError();
+    return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "large_var_hess = 1: %s (%zu B): %s", what, bytes, hipGetErrorString(e));
+}
+static int var_large_hess_enable(pcl_ctx *ctx) {
+    if (ctx->dlhpart && ctx->dellt_col && ctx->dellt_val && ctx->dvl_gtcol && ctx->dvl_gtval) return PCL_OK;
+    ON_DEVICE(ctx);
+    const int n = ctx->n, m = ctx->desc.n_drives, v = ctx->var, nl = ctx->var_nl;
+    // rows of A^T = columns of A, entries in ascending row order, zero padded to the widest
+    auto rows_t = [&](int cnt, auto at, int floor_w, std::vector<int> &col, std::vector<double> &val) {
+        int wd = floor_w;
+        for (int t = 0; t < cnt; ++t)
+            for (int i = 0; i < n; ++i) {
+                int c = 0;
+                for (int j = 0; j < n; ++j) c += at(t, j, i) != 0.0;
+                wd = std::max(wd, c);
+            }
+        col.assign((size_t)cnt * n * wd, 0);
+        val.assign((size_t)cnt * n * wd, 0.0);
+        for (int t = 0; t < cnt; ++t)
+            for (int i = 0; i < n; ++i) {
+                size_t e = ((size_t)t * n + i) * wd;
+                for (int j = 0; j < n; ++j)
+                    if (at(t, j, i) != 0.0) col[e] = j, val[e] = at(t, j, i), ++e;
+            }
+        return wd;
+    };
+    std::vector<int> dcol, gcol;
+    std::vector<double> dval, gval;
+    const int etw = rows_t(m, [&](int l, int r, int c) { return ctx->hGj[(size_t)l * nl * nl + r + (size_t)nl * c]; }, m > 0 ? 1 : 0, dcol, dval);
+    const int gtw = rows_t(v, [&](int b, int r, int c) { return ctx->hG0[(size_t)((b + 1) * n + r) + (size_t)nl * c]; }, 1, gcol, gval);
+    struct Up {
+        void **dst;
+        const void *src;
+        size_t bytes;
+        const char *what;
+    } ups[] = {{(void **)&ctx->dellt_col, dcol.data(), dcol.size() * sizeof(int), "the transposed drive rows"},
+               {(void **)&ctx->dellt_val, dval.data(), dval.size() * sizeof(double), "the transposed drive rows"},
+               {(void **)&ctx->dvl_gtcol, gcol.data(), gcol.size() * sizeof(int), "the transposed variation rows"},
+               {(void **)&ctx->dvl_gtval, gval.data(), gval.size() * sizeof(double), "the transposed variation rows"}};
+    for (const Up &u : ups) {
+        if (*u.dst) continue;
+        TRY(var_large_hess_alloc(ctx, u.dst, u.bytes, u.what));
+        if (u.bytes) HIP_TRY(ctx, hipMemcpy(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice));
+    }
+    ctx->vl_etw = etw;
+    ctx->vl_gtw = gtw;
+    if (!ctx->dlhpart)
+        TRY(var_large_hess_alloc(ctx, (void **)&ctx->dlhpart, (size_t)ctx->K * ctx->cols * ((size_t)m * (m + 1) + 1) * sizeof(double), "the workspace of the partial sums"));
+    return PCL_OK;
+}
+static int launch_var_large_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    if (ctx->desc.pade_order == 0)
+        return fail(ctx, PCL_EINVAL, "pcl_hess: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");
+    if (!ctx->large_var_hess || !ctx->dlhpart) return fail(ctx, PCL_EINVAL, "pcl_hess: option large_var_hess is off");
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var;
+    LargeHessPlan P;
+    var_large_hess_plan(ctx, n, ctx->cols, m, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large variational Hessian kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, n, m);
+    KParams p;
+    memset(&p, 0, sizeof p);
+    fill_pade(p, D.pade_order);
+    p.Z = Z;
+    p.mu = mu;
+    p.hess = hess;
+    p.hpart = ctx->dlhpart;
+    p.G0 = ctx->dvar_tab;
+    p.upos = ctx->dupos;
+    p.ucoef = ctx->ducoef;
+    p.n_upos = ctx->n_upos;
+    p.ell_val = ctx->dell_val;
+    p.ell_col = ctx->dell_col;
+    p.ell_w = ctx->ell_w;
+    p.ellt_val = ctx->dellt_val;
+    p.ellt_col = ctx->dellt_col;
+    p.ellt_w = ctx->vl_etw;
+    p.x_off0 = -1;
+    p.hess_per = hess_per(ctx);
+    p.d = D.d;
+    p.n = n;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.batch = 1;
+    p.cols = ctx->cols;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.LD = P.LD;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    VarLargeHessParams w;
+    memset(&w, 0, sizeof w);
+    w.gv_val = ctx->dvl_gval;
+    w.gv_col = ctx->dvl_gcol;
+    w.gv_w = ctx->vl_gw;
+    w.gvt_val = ctx->dvl_gtval;
+    w.gvt_col = ctx->dvl_gtcol;
+    w.gvt_w = ctx->vl_gtw;
+    w.v = v;
+    for (int b = 0; b <= v; ++b) w.xo[b] = ctx->x_offs[b];
+    w.sx = P.sx;
+    w.mg = P.mg;
+    const long long items = ctx->K, grid = items * P.U;
+    if (int rc = check_grid(ctx, grid)) return rc;
+    if (int rc = var_set_lds(ctx, (const void *)pcl_var_large_hess_kernel, P.lds)) return rc;
+    hipLaunchKernelGGL(pcl_var_large_hess_kernel, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, w);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(pcl_pade_large_hess_sum_kernel, dim3((unsigned)items), dim3(256), 0, ctx->stream, p);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_hess_kernel = 340 + p.q;  // the large variational Hessian kernel
+    return PCL_OK;
+}
+
 // Hessian of the Lagrangian of a large exponential context (pcl_kernel_large_exp_hess.hpp; option large_exp_hess).  The plan, next to
 // large_exp_plan (pcl_host_launch_pade.hpp): LD = n | 1, 64 threads per 16-row tile; what the tile leaves of the LDS is NB column blocks of LD
 // doubles, a third of them (NBW) per rotating buffer.  A unit of nc state columns and a pair of drive groups of mg drives holds, per state column,
@@ -522,6 +677,7 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
     TRY(require(ctx, FEAT_HESS, "pcl_hess"));
+    if (ctx->large_var) return launch_var_large_hess(ctx, Z, mu, hess);
     if (ctx->large_exp) return launch_large_exp_hess(ctx, Z, mu, hess);
     if (ctx->large) return launch_pade_large_hess(ctx, Z, mu, hess);
     if (ctx->exp) return launch_exp_hess(ctx, Z, mu, hess);

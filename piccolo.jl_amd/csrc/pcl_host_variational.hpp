@@ -8,6 +8,7 @@
 #include "pcl_kernel_var_exp_hess.hpp"
 #include "pcl_kernel_var_exp_hess_tiles.hpp"
 #include "pcl_kernel_var_large.hpp"
+#include "pcl_kernel_var_large_hess.hpp"
 #include "pcl_kernel_var_large_rollout.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).

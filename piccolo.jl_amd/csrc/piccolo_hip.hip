@@ -8,6 +8,7 @@
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
 //   pcl_kernel_large_exp_hess.hpp   ... its Hessian of the Lagrangian (option large_exp_hess): the adjoint of that recurrence with the second derivative carried, per-column partial sums
 //   pcl_kernel_var_large.hpp        ... the variational integrators there (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR): chain units of 1 + v components, panel units of the powers and, one variation at a time, the Frechet powers
+//   pcl_kernel_var_large_hess.hpp   ... ... their Hessian of the Lagrangian (option large_var_hess): the chains of pcl_kernel_pade_large_hess.hpp on the lifted generator, one pass per component
 //   pcl_kernel_var_large_rollout.hpp ... ... their rollout of the stacked state (option large_var_full): E and the Frechet derivatives L_i by column panels of one substepped Horner recurrence, then the chain of the knots
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
@@ -122,6 +123,11 @@ struct pcl_ctx {
     int *dvl_gcol = nullptr;              // ... ... the variation generators row-compressed, [v][n][vl_gw] (row-major, zero padded)
     double *dvl_gval = nullptr;
     int vl_gw = 0;
+    int large_var_hess = 0;               // ... ... option large_var_hess: the Hessian of the Lagrangian is served (pcl_kernel_var_large_hess.hpp; its workspace is dlhpart, its tables dellt_* and the two below)
+    int64_t opt_large_var_hess_drives = 0;  // ... ... ... the most drives per group of that launch (0 auto: as many as fit)
+    int *dvl_gtcol = nullptr;             // ... ... ... the transposed variation generators row-compressed, [v][n][vl_gtw] (allocated when the option is first set to 1)
+    double *dvl_gtval = nullptr;
+    int vl_gtw = 0, vl_etw = 0;           // ... ... ... the widths of those rows and of the transposed drive rows (dellt_*)
     int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
     int var_compact = 0;         // ... option var_compact: the compact Jacobian trio and the host expansion are served (either constraint kind)
     std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
@@ -754,7 +760,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart, ctx->dvl_gcol, ctx->dvl_gval};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart, ctx->dvl_gcol, ctx->dvl_gval, ctx->dvl_gtcol, ctx->dvl_gtval};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);

@@ -75,8 +75,12 @@ def _ptr(a):
 # large_var_full     beside ``large_generator=True`` on a variational constructor (Pade constraint): the robust-control objective family -- goals,
 #                    weights, regularisers, value, gradient, the objective's Hessian -- and the rollout of the stacked state at dimensions
 #                    66 .. 128 (option ``large_var_full``): ``Objective.bind``, ``rollout``, ``rollout_dev``, ``variational_rollout`` work.  The
-#                    Hessian of the Lagrangian and the compact Jacobian stay refused there.  At a dimension up to 64 it sets nothing (``var_full``,
-#                    which ``enable_objective_and_rollout`` switches on, is that context's option).
+#                    compact Jacobian stays refused there.  At a dimension up to 64 it sets nothing (``var_full``, which
+#                    ``enable_objective_and_rollout`` switches on, is that context's option).
+# large_var_hessian  beside ``large_generator=True`` on a variational constructor (Pade constraint): the Hessian of the Lagrangian at dimensions
+#                    66 .. 128 (option ``large_var_hess``; values, order and structure are the variational context's at dimensions up to 64):
+#                    ``hess``, ``hess_dev``, ``hess_structure``, ``hessian_structure``, ``eval_hessian_of_lagrangian`` work.  At a dimension up to
+#                    64 it sets nothing (the ordinary variational context serves its Hessian always).
 # large_hessian      beside ``large_generator=True`` on the plain Pade constraint: the Hessian of the Lagrangian there (option ``large_hess``).
 # large_full         the same conditions, or beside ``large_exp=True``: the objective family -- goals, weights, regularisers, value, gradient, the
 #                    objective's Hessian -- and the rollout there (option ``large_full``): ``rollout``, ``rollout_dev``, ``Objective.bind`` work.
@@ -115,6 +119,11 @@ _SERVICES = (
                   "VariationalKetIntegrator with large_generator=True): a plain context takes large_full=True",
         "beside": "large_var_full=True is the objective and the rollout of a variational context created with large_generator=True: it needs that keyword",
         "constraint": "large_var_full=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"}),
+    _Service("large_var_hessian", option="large_var_hess", beside="large_generator", constraint="pade context", family="variational", sizes="hess", at="large_variational", refuse={
+        "family": "large_var_hessian=True is the Hessian of the Lagrangian of a large variational context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator with large_generator=True): a plain context takes large_hessian=True",
+        "beside": "large_var_hessian=True is the Hessian of the Lagrangian of a variational context created with large_generator=True: it needs that keyword",
+        "constraint": "large_var_hessian=True serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"}),
     _Service("large_exp_hessian", option="large_exp_hess", beside="large_exp", family="plain", sizes="hess", at="large_exp", refuse={
         "family": "large_exp_hessian=True is not served on a variational context (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)",
         "beside": "large_exp_hessian=True is the Hessian of the Lagrangian of a context created with large_exp=True "
@@ -158,7 +167,7 @@ _SERVICES = (
 )
 _BY_OPTION = {row.option: row for row in _SERVICES if row.option}
 # the order in which a constructor switches the options on (the tile plan before the Hessian that reads it)
-_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "large_var_full", "var_compact")
+_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "large_var_full", "large_var_hess", "var_compact")
 _VARIATIONAL_MODES = (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
 
 
@@ -196,10 +205,11 @@ class _PclContext:
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False, large_variational=False, large_var_full=False):  # fmt: skip
+                 large_exp_reduce=False, large_variational=False, large_var_full=False, large_var_hessian=False):  # fmt: skip
         keywords = dict(exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact, large_generator=large_generator, large_hessian=large_hessian,
                         large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
-                        large_exp_reduce=large_exp_reduce, large_variational=large_variational, large_var_full=large_var_full)  # fmt: skip
+                        large_exp_reduce=large_exp_reduce, large_variational=large_variational, large_var_full=large_var_full,
+                        large_var_hessian=large_var_hessian)  # fmt: skip
         keywords["exp_hessian"] = _check_services(batch_mode, pade_order, **keywords)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         self._L = _lib.load()
@@ -733,19 +743,19 @@ class HipVariationalIntegrator:
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
     derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian`` switches them on.
 
-    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator`` and ``large_var_full``: what each serves is
+    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator``, ``large_var_full`` and ``large_var_hessian``: what each serves is
     said once, above ``_SERVICES`` in this module.  The other large keywords are accepted and, switched on, refused in the table's words."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
-                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False):
+                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False, large_var_hessian=False):
         pade_order = _lib.order_code(pade_order)
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         batch_mode = PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL
         exp_hessian = _check_services(batch_mode, pade_order, exp_hessian=exp_hessian, var_compact=var_compact, large_generator=large_generator,
                                       large_variational=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
                                       large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce,
-                                      large_var_full=large_var_full)  # fmt: skip
+                                      large_var_full=large_var_full, large_var_hessian=large_var_hessian)  # fmt: skip
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -777,6 +787,7 @@ class HipVariationalIntegrator:
             batch=len(names), batch_mode=batch_mode, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
             large_generator=bool(large_generator), large_variational=bool(large_generator), large_var_full=bool(large_var_full),
+            large_var_hessian=bool(large_var_hessian),
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)

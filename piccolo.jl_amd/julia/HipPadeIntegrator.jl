@@ -329,17 +329,21 @@ end
 #      through the compact ones (every distinct tile once over PCIe, replicated by the host's threads) where the blocks are replicated;
 #      off by default, never on by itself.
 #      large_generator = true: the library's flags PCL_LARGE_N | PCL_LARGE_VAR in batch_mode -- generator dimensions 66 .. 128 on the Pade
-#      constraint: residual and Jacobian; no Hessian of the Lagrangian (the structure stays empty, solve with eval_hessian = false), no
+#      constraint: residual and Jacobian; no Hessian of the Lagrangian unless large_var_hessian = true (the structure stays empty, solve with eval_hessian = false), no
 #      objective or rollout from the library unless large_var_full = true.  With pade_order = :exp: ArgumentError.  At 64 and below it
 #      changes nothing; never on by itself.
 #      large_var_full = true (with large_generator = true on the Pade constraint only): the library's option large_var_full -- the
 #      robust-control objective family and the rollout of the stacked state at generator dimensions 66 .. 128; _enable_var_full! then does
 #      nothing there (without the keyword it raises the library's message naming PCL_LARGE_VAR, as before).  At 64 and below it sets nothing.
+#      large_var_hessian = true (with large_generator = true on the Pade constraint only): the library's option large_var_hess -- the Hessian
+#      of the Lagrangian at generator dimensions 66 .. 128, with the values, order and structure of the variational context at 64 and below
+#      (the structure is then filled as there).  At 64 and below it sets nothing (that context serves its Hessian always).
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
                       var_compact::Bool = false, large_generator::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false,
-                      large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false, large_var_full::Bool = false)
+                      large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false, large_var_full::Bool = false,
+                      large_var_hessian::Bool = false)
     large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
@@ -354,6 +358,10 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
         throw(ArgumentError("HipPadeIntegrator: large_var_full = true is the objective and the rollout of a variational context created with large_generator = true: it needs that keyword"))
     (large_var_full && expo) &&
         throw(ArgumentError("HipPadeIntegrator: large_var_full = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"))
+    (large_var_hessian && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_hessian = true is the Hessian of the Lagrangian of a variational context created with large_generator = true: it needs that keyword"))
+    (large_var_hessian && expo) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_hessian = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"))
     (exp_hessian isa Symbol && exp_hessian != :workspace) &&
         throw(ArgumentError("HipPadeIntegrator: exp_hessian must be false, true or :workspace (got :$(exp_hessian))"))
     workspace = exp_hessian === :workspace
@@ -385,9 +393,10 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     workspace && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess_tiles", 1))
     exp_hessian && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_exp_hess", 1))
     var_compact && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "var_compact", 1))
-    large_var = large_generator && size(G0, 1) > 64                   # (a large variational context: the Hessian of the Lagrangian is refused)
+    large_var = large_generator && size(G0, 1) > 64                   # (a large variational context: the Hessian of the Lagrangian is refused without large_var_hessian)
     (large_var && large_var_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_full", 1))
-    ((expo && !exp_hessian) || large_var) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    (large_var && large_var_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_hess", 1))
+    ((expo && !exp_hessian) || (large_var && !large_var_hessian)) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
