@@ -124,6 +124,28 @@ static long long balanced_grid(long long items, long long slots, int64_t opt_gri
     const long long rounds = (items + slots - 1) / slots;
     return opt_grid > 0 ? std::min<long long>(items, opt_grid) : (items + rounds - 1) / rounds;
 }
+// The tile geometry of the large-generator kernels (pcl_device_large.hpp), stated once for their planners: LD = n | 1, 64 threads per 16-row tile of
+// G, `fixed` doubles of LDS whatever the plan (the tile, PL_SLACK, the drive amplitudes of build_G) and, in what they leave of max_lds, NB column
+// blocks of LD doubles.  Every plan of the family starts from it (struct ...Plan : LargeTile)
+struct LargeTile {
+    int LD, threads;
+    long long fixed;
+    int NB;
+};
+static LargeTile large_tile(int max_lds, int n, int m) {
+    LargeTile t;
+    t.LD = n | 1;
+    t.threads = 64 * ((n + 15) / 16);
+    t.fixed = (long long)t.LD * n + PL_SLACK + m + 8;
+    t.NB = (int)((max_lds / (long long)sizeof(double) - t.fixed) / t.LD);
+    return t;
+}
+// `total` in pieces of at most `per` (state columns in slices, drives in groups): returns the fewest pieces and evens `per` over them
+static int even_split(int total, int &per) {
+    const int cnt = (total + per - 1) / per;
+    per = (total + cnt - 1) / cnt;
+    return cnt;
+}
 // Grow-only device scratch: nothing while *cap covers `need`; else a (and b, which shares the capacity) are freed and allocated anew with na / nb
 // elements, zero-filled on the launch stream where asked, and *cap is set last: a failed allocation leaves no capacity behind.
 template <class C, class A, class B = char>

@@ -6,38 +6,34 @@
 // four families of accumulators) and nc (mg (m + 1) + 1) partial sums.  The widest nc that leaves room for one drive is taken (option
 // cols_per_slice caps it), then the most drives per group that fit (option large_hess_drives caps them); slices and groups are evened.  One
 // column and one drive always fit (n = 128, m = 24: 148,032 B).  Every split gives the same bits.
-struct LargeHessPlan {
-    int LD, threads, sx, nc, mg, ngrp, U;
+struct LargeHessPlan : LargeTile {
+    int sx, nc, mg, ngrp, U;
     size_t lds;
 };
-static size_t large_hess_lds_bytes(int n, int m, int nc, int mg) {
-    const size_t LD = (size_t)(n | 1);
-    return (LD * n + LD * nc * (10 + 4 * (size_t)mg) + PL_SLACK + m + 8 + (size_t)nc * ((size_t)mg * (m + 1) + 1)) * sizeof(double);
+static size_t large_hess_lds_bytes(const LargeTile &t, int m, int nc, int mg) {
+    return (size_t)(t.fixed + (long long)t.LD * nc * (10 + 4 * mg) + (long long)nc * ((long long)mg * (m + 1) + 1)) * sizeof(double);
 }
 static void large_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeHessPlan &P) {
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
     const int mg_cap = m > 0 ? (ctx->opt_large_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_hess_drives, m) : m) : 0;
     const int mg_min = m > 0 ? 1 : 0;
     P.nc = 1;
     for (int nc = nc_cap; nc > 1; --nc)
-        if (large_hess_lds_bytes(n, m, nc, mg_min) <= (size_t)ctx->max_lds) {
+        if (large_hess_lds_bytes(P, m, nc, mg_min) <= (size_t)ctx->max_lds) {
             P.nc = nc;
             break;
         }
     P.mg = mg_min;
     for (int mg = mg_cap; mg > mg_min; --mg)
-        if (large_hess_lds_bytes(n, m, P.nc, mg) <= (size_t)ctx->max_lds) {
+        if (large_hess_lds_bytes(P, m, P.nc, mg) <= (size_t)ctx->max_lds) {
             P.mg = mg;
             break;
         }
-    P.ngrp = m > 0 ? (m + P.mg - 1) / P.mg : 1;
-    if (m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
-    P.sx = (cols + P.nc - 1) / P.nc;
-    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.ngrp = m > 0 ? even_split(m, P.mg) : 1;  // even groups
+    P.sx = even_split(cols, P.nc);             // even slices
     P.U = P.sx * P.ngrp;
-    P.lds = large_hess_lds_bytes(n, m, P.nc, P.mg);
+    P.lds = large_hess_lds_bytes(P, m, P.nc, P.mg);
 }
 static int large_hess_enable(pcl_ctx *ctx) {
     if (!ctx->dlhpart) {
@@ -81,34 +77,30 @@ static int launch_pade_large_hess(pcl_ctx *ctx, const double *Z, const double *m
 // tile -- and the same partial sums: the widest nc that leaves room for one drive (option cols_per_slice caps it), then the most drives per group
 // that fit (option large_var_hess_drives caps them), slices and groups evened.  One column and one drive always fit (n = 128, m = 24: 162,480 B).
 // Every split gives the same bits.
-static size_t var_large_hess_lds_bytes(int n, int m, int nc, int mg) {
-    const size_t LD = (size_t)(n | 1);
-    return (LD * n + LD * nc * (20 + 8 * (size_t)mg) + PL_SLACK + m + 8 + (size_t)nc * ((size_t)mg * (m + 1) + 1)) * sizeof(double);
+static size_t var_large_hess_lds_bytes(const LargeTile &t, int m, int nc, int mg) {
+    return (size_t)(t.fixed + (long long)t.LD * nc * (20 + 8 * mg) + (long long)nc * ((long long)mg * (m + 1) + 1)) * sizeof(double);
 }
 static void var_large_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeHessPlan &P) {
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
     const int mg_cap = m > 0 ? (ctx->opt_large_var_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_var_hess_drives, m) : m) : 0;
     const int mg_min = m > 0 ? 1 : 0;
     P.nc = 1;
     for (int nc = nc_cap; nc > 1; --nc)
-        if (var_large_hess_lds_bytes(n, m, nc, mg_min) <= (size_t)ctx->max_lds) {
+        if (var_large_hess_lds_bytes(P, m, nc, mg_min) <= (size_t)ctx->max_lds) {
             P.nc = nc;
             break;
         }
     P.mg = mg_min;
     for (int mg = mg_cap; mg > mg_min; --mg)
-        if (var_large_hess_lds_bytes(n, m, P.nc, mg) <= (size_t)ctx->max_lds) {
+        if (var_large_hess_lds_bytes(P, m, P.nc, mg) <= (size_t)ctx->max_lds) {
             P.mg = mg;
             break;
         }
-    P.ngrp = m > 0 ? (m + P.mg - 1) / P.mg : 1;
-    if (m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
-    P.sx = (cols + P.nc - 1) / P.nc;
-    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.ngrp = m > 0 ? even_split(m, P.mg) : 1;  // even groups
+    P.sx = even_split(cols, P.nc);             // even slices
     P.U = P.sx * P.ngrp;
-    P.lds = var_large_hess_lds_bytes(n, m, P.nc, P.mg);
+    P.lds = var_large_hess_lds_bytes(P, m, P.nc, P.mg);
 }
 // option large_var_hess = 1: the workspace of the partial sums and the transposed row tables of the drives and of the variation generators
 // (allocated here, on first use, not by pcl_create; the tables come from the lifted host copies the order policy keeps)
@@ -242,16 +234,13 @@ static int launch_var_large_hess(pcl_ctx *ctx, const double *Z, const double *mu
 //     sx (ngrp ceil(nc Td / 16) + ngrp (ngrp - 1) / 2 ceil(nc To / 16)),
 // on a tie the fewest units, then the wider slice and the larger group.  U = sx ngrp (ngrp + 1) / 2 units per interval.  The smallest unit needs
 // 4 columns per buffer; n = 128 has 9, so nothing is refused for m <= 24, n <= 128.  Every split gives the same bits.
-struct LargeExpHessPlan {
-    int LD, threads, NB, NBW, sx, nc, mg, ngrp, U, W;
+struct LargeExpHessPlan : LargeTile {
+    int NBW, sx, nc, mg, ngrp, U, W;
     long long passes;
     size_t lds;
 };
 static void large_exp_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeExpHessPlan &P) {
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
-    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
-    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     P.NBW = P.NB / 3;
     const int t_min = m == 0 ? 2 : (m == 1 ? 3 : 4);  // the narrowest unit: no drives | one drive | two groups of one
     const int nc_fit = std::max(1, P.NBW / t_min);
@@ -261,9 +250,11 @@ static void large_exp_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, Larg
     long long best_p = -1, best_u = -1;
     P.sx = cols, P.nc = 1, P.mg = m > 0 ? 1 : 0, P.ngrp = std::max(m, 1), P.W = t_min;
     for (int nc0 = nc_hi; nc0 >= nc_lo; --nc0) {
-        const int sx = (cols + nc0 - 1) / nc0, nc = (cols + sx - 1) / sx;  // even slices
+        int nc = nc0;
+        const int sx = even_split(cols, nc);  // even slices
         for (int mg0 = mg_cap; mg0 >= (m > 0 ? 1 : 0); --mg0) {
-            const int ngrp = m > 0 ? (m + mg0 - 1) / mg0 : 1, mg = m > 0 ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            int mg = mg0;
+            const int ngrp = m > 0 ? even_split(m, mg) : 1;  // even groups
             const int Td = m > 0 ? 1 + mg + mg * (mg + 1) / 2 : 2, To = 1 + 2 * mg + mg * mg;
             const int W = nc * (ngrp > 1 ? To : Td);
             if (W > P.NBW) continue;
@@ -275,7 +266,7 @@ static void large_exp_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, Larg
     }
     P.passes = best_p;
     P.U = P.sx * (P.ngrp * (P.ngrp + 1) / 2);
-    P.lds = (size_t)(fixed + 3LL * P.LD * P.W) * sizeof(double);
+    P.lds = (size_t)(P.fixed + 3LL * P.LD * P.W) * sizeof(double);
 }
 static int large_exp_hess_enable(pcl_ctx *ctx) {
     if (!ctx->dlehpart) {

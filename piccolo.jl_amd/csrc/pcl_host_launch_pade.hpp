@@ -181,15 +181,12 @@ static int launch_pade_v2(pcl_ctx *ctx, KParams &p) {
 // and, for launches of few intervals, up to one unit per 16 power columns while the grid stays within one round of the CUs (option
 // general_slices: that many units at least).  Every split gives the same bits.
 // The payload-only launch (option large_reduce, pcl_eval_jac_merit_dev without values): the same chain units and nothing else -- U = sx ngrp, npc = 0.
-struct LargePlan {
-    int LD, threads, NB, sx, nc, mg, ngrp, U, npc;
+struct LargePlan : LargeTile {
+    int sx, nc, mg, ngrp, U, npc;
     size_t lds;
 };
 static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargePlan &P, bool payload_only = false) {
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
-    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
-    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
     P.nc = 1, P.mg = jac && m > 0 ? 1 : 0;
     for (int nc = nc_cap; nc >= 1; --nc) {
@@ -204,10 +201,8 @@ static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, lon
         P.mg = m > 0 ? std::max(mg_max, 1) : 0;
         break;
     }
-    P.ngrp = jac && m > 0 ? (m + P.mg - 1) / P.mg : 1;
-    if (jac && m > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
-    P.sx = (cols + P.nc - 1) / P.nc;
-    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.ngrp = jac && m > 0 ? even_split(m, P.mg) : 1;  // even groups
+    P.sx = even_split(cols, P.nc);                    // even slices
     const int chain_units = P.sx * P.ngrp, chain_blocks = P.nc * (jac ? 2 + 2 * (2 + P.mg) : 4);
     P.U = chain_units;
     P.npc = 0;
@@ -223,7 +218,7 @@ static void large_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, lon
         P.npc = (n + P.U - 1) / P.U;
         P.U = std::max(chain_units, (n + P.npc - 1) / P.npc);  // (no unit without work)
     }
-    P.lds = (size_t)(fixed + (long long)P.LD * (chain_blocks + P.npc)) * sizeof(double);
+    P.lds = (size_t)(P.fixed + (long long)P.LD * (chain_blocks + P.npc)) * sizeof(double);
 }
 // mode (option large_reduce): PL_FULL | PL_COMPACT | PL_MERIT (p.mpart, p.mlam set) | PL_PAYLOAD (the same, no values) -- pcl_kernel_pade_large.hpp
 static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac, int mode = PL_FULL) {
@@ -266,28 +261,25 @@ static int launch_pade_large(pcl_ctx *ctx, KParams &p, bool want_jac, int mode =
 // The payload-only launch (option large_exp_reduce, pcl_eval_jac_merit_dev without values; mode LE_PAYLOAD): the slices of the Jacobian plan, chain
 // units alone -- no column of E, so a group may fill a buffer: nc (1 + mg) <= NBW (option large_exp_drives caps mg) -- chosen by the same count
 // (tile passes times rounds of the grid, then the fewest passes, then the larger group); U = sx ngrp, npc = 0, LDS = fixed + 3 LD nc (1 + mg).
-struct LargeExpPlan {
-    int LD, threads, NB, NBW, sx, nc, mg, ngrp, U, npc, W;
+struct LargeExpPlan : LargeTile {
+    int NBW, sx, nc, mg, ngrp, U, npc, W;
     size_t lds;
 };
 static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac, long long items, LargeExpPlan &P, bool payload_only = false) {
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
-    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
-    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     P.NBW = P.NB / 3;
     const bool drv = jac && m > 0;
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16);
     P.nc = std::max(1, std::min(nc_cap, (P.NBW - (jac ? 1 : 0)) / (drv ? 2 : 1)));
-    P.sx = (cols + P.nc - 1) / P.nc;
-    P.nc = (cols + P.sx - 1) / P.sx;  // even slices
+    P.sx = even_split(cols, P.nc);  // even slices
     P.mg = 0, P.ngrp = 1, P.U = P.sx, P.npc = 0;
     if (jac && payload_only) {
         int mg_fit = drv ? std::max(1, std::min(m, P.NBW / P.nc - 1)) : 0;
         if (drv && ctx->opt_large_exp_drives > 0) mg_fit = (int)std::min<int64_t>(mg_fit, ctx->opt_large_exp_drives);
         long long best_t = -1, best_p = -1;
         for (int mg0 = mg_fit; mg0 >= (drv ? 1 : 0); --mg0) {
-            const int ngrp = drv ? (m + mg0 - 1) / mg0 : 1, mg = drv ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            int mg = mg0;
+            const int ngrp = drv ? even_split(m, mg) : 1;  // even groups
             const int U = P.sx * ngrp;
             const long long tiles = (P.nc * (1 + mg) + 15) / 16, rounds = (std::max(items, 1LL) * U + ctx->n_cu - 1) / std::max(ctx->n_cu, 1);
             const long long t = tiles * rounds, passes = tiles * U;
@@ -300,7 +292,8 @@ static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac,
         // per group size two candidates: the fewest units that fit, and the fewest whose columns of E end with the chain's last column tile
         long long best_t = -1, best_p = -1;
         for (int mg0 = mg_fit; mg0 >= (drv ? 1 : 0); --mg0) {
-            const int ngrp = drv ? (m + mg0 - 1) / mg0 : 1, mg = drv ? (m + ngrp - 1) / ngrp : 0;  // even groups
+            int mg = mg0;
+            const int ngrp = drv ? even_split(m, mg) : 1;  // even groups
             const int cx = P.nc * (1 + mg), npc_max = std::max(1, std::min(n, P.NBW - cx)), npc_16 = std::min(npc_max, 16 * (cx / 16 + 1) - cx);
             for (int cand = 0; cand < 2; ++cand) {
                 const int npc0 = cand ? npc_16 : npc_max;
@@ -317,7 +310,7 @@ static void large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, bool jac,
         P.U = std::max(chain_units, (n + P.npc - 1) / P.npc);  // (no unit without work)
     }
     P.W = P.nc * (1 + P.mg) + P.npc;
-    P.lds = (size_t)(fixed + 3LL * P.LD * P.W) * sizeof(double);
+    P.lds = (size_t)(P.fixed + 3LL * P.LD * P.W) * sizeof(double);
 }
 // mode (option large_exp_reduce): LE_FULL | LE_COMPACT | LE_MERIT (p.mpart, p.mlam set) | LE_PAYLOAD (the same, no values) -- pcl_kernel_large_exp.hpp
 static int launch_large_exp(pcl_ctx *ctx, KParams &p, bool want_jac, int mode = LE_FULL) {

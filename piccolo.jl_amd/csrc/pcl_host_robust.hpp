@@ -314,16 +314,14 @@ static int var_objective_hess_dev(pcl_ctx *ctx, const double *Z, double Q, doubl
 // (1 + v) roles stays within one round of the CUs (option general_slices: that many panels per role at least).  The chain takes slices of 16
 // state columns, one matrix-core column tile (option cols_per_slice: that many at most, never more than 16).  One column always fits
 // (n = 128, m = 24: 139,568 B and 5,152 B).  Every split gives the same bits.
-struct VarLargeRollPlan {
-    int LD, threads, P, npc, S, nc;
+struct VarLargeRollPlan : LargeTile {
+    int P, npc, S, nc;
     size_t lds_e, lds_c;
 };
 static void var_large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, long long K, VarLargeRollPlan &R) {
-    R.LD = n | 1;
-    R.threads = 64 * ((n + 15) / 16);
-    const long long budget = ctx->max_lds / (long long)sizeof(double), tile = (long long)R.LD * n;
-    const long long fixed_e = tile + PL_SLACK + m + 8, fixed_c = PL_SLACK;
-    const int npc_max = (int)std::max<long long>(1, std::min<long long>(n, (budget - fixed_e) / R.LD / 6));
+    static_cast<LargeTile &>(R) = large_tile(ctx->max_lds, n, m);  // (the propagator launch's; the chain launch has the slack alone.  NB >= 0: the tile fits for n <= 128)
+    const long long budget = ctx->max_lds / (long long)sizeof(double), fixed_c = PL_SLACK;
+    const int npc_max = std::max(1, std::min(n, R.NB / 6));
     const int p_min = (n + npc_max - 1) / npc_max;
     const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices : std::min<long long>((n + 15) / 16, ctx->n_cu / std::max(K * (1 + v), 1LL));
     R.P = (int)std::max<long long>(p_min, std::min<long long>(want, n));
@@ -333,7 +331,7 @@ static void var_large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, int 
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
     R.nc = std::min(std::min(nc_cap, nc_fit), 16);
     R.S = (cols + R.nc - 1) / R.nc;
-    R.lds_e = (size_t)(fixed_e + 6LL * R.LD * R.npc) * sizeof(double);
+    R.lds_e = (size_t)(R.fixed + 6LL * R.LD * R.npc) * sizeof(double);
     R.lds_c = (size_t)(fixed_c + 4LL * R.LD * R.nc) * sizeof(double);
 }
 static int var_large_rollout_dev(pcl_ctx *ctx, const double *Z, double *X_out) {

@@ -604,16 +604,13 @@ static int var_exp_launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, 
 // narrower slices while the chain units stay within half a round of the CUs.  Panel units are workgroups of their own, (1 + v) pu of them: npc
 // columns of the powers need three blocks each (P', Q, Q') and a thread owns at most PL_NP pairs; one unit per 16 columns at least (option
 // general_slices: that many units per role at least).  Every split gives the same bits.
-struct VarLargePlan {
-    int LD, threads, NB, sx, nc, mg, ngrp, chain_units, chain_blocks, npc, pu, U;
+struct VarLargePlan : LargeTile {
+    int sx, nc, mg, ngrp, chain_units, chain_blocks, npc, pu, U;
     size_t lds;
 };
 static void var_large_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, bool jac, long long items, VarLargePlan &P) {
     const int comp = 1 + v;
-    P.LD = n | 1;
-    P.threads = 64 * ((n + 15) / 16);
-    const long long fixed = (long long)P.LD * n + PL_SLACK + m + 8;
-    P.NB = (int)((ctx->max_lds / (long long)sizeof(double) - fixed) / P.LD);
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : cols;
     const int mg_cap = jac && m > 0 ? (ctx->opt_var_large_drives > 0 ? (int)std::min<int64_t>(ctx->opt_var_large_drives, m) : m) : 0;
     auto blocks = [&](int nc, int mg) { return comp * nc * (jac ? 2 + 2 * (2 + mg) : 4); };
@@ -625,8 +622,7 @@ static void var_large_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, bo
         }
     P.mg = mg_cap;
     while (P.mg > 1 && blocks(P.nc, P.mg) > P.NB) --P.mg;  // (one column only: the most drives that fit)
-    P.ngrp = mg_cap > 0 ? (m + P.mg - 1) / P.mg : 1;
-    if (mg_cap > 0) P.mg = (m + P.ngrp - 1) / P.ngrp;  // even groups
+    P.ngrp = mg_cap > 0 ? even_split(m, P.mg) : 1;  // even groups
     P.sx = (cols + P.nc - 1) / P.nc;
     const long long want_sx = ctx->n_cu / std::max(2 * items * P.ngrp, 1LL);
     if (want_sx > P.sx) P.sx = (int)std::min<long long>(want_sx, cols);
@@ -648,7 +644,7 @@ static void var_large_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, bo
         P.pu = (n + P.npc - 1) / P.npc;  // (no unit without work)
     }
     P.U = P.chain_units + comp * P.pu;
-    P.lds = (size_t)(fixed + (long long)P.LD * std::max(P.chain_blocks, 3 * P.npc)) * sizeof(double);
+    P.lds = (size_t)(P.fixed + (long long)P.LD * std::max(P.chain_blocks, 3 * P.npc)) * sizeof(double);
 }
 static int var_large_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
     const pcl_desc &D = ctx->desc;

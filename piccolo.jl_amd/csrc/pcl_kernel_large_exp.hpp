@@ -93,7 +93,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
     const int sp = x == 0.0 ? 0 : (x <= (double)LR_SMAX * LR_THETA ? (int)ceil(x / LR_THETA) : LR_SMAX);
     const double hs = sp > 0 ? h / sp : 0.0;
     double a[PL_KS];
-    const unsigned kmask = lr_load_a(G, LD, n, rt, li, lk, a);
+    const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     __syncthreads();  // (the norms have been read)
     if (tid < n) B2[tid] = 0.0;
     for (int e = tid; e < nce * n; e += nth) {  // Y = X_k; the dY blocks stay zero
@@ -125,12 +125,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
                         const double *wc = V + LD * c;
                         const long long lrow = (long long)(l0 + bl - 1) * n;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * ew;
-                            double v = 0.0;
-                            for (int e = 0; e < ew; ++e) v = __builtin_fma(p.ell_val[eb + e], wc[p.ell_col[eb + e]], v);
-                            y[r] = v;
-                        }
+                        for (int r = 0; r < 4; ++r) y[r] = pl_row_dot(p.ell_val, p.ell_col, (lrow + min(r0 + 4 * r, n - 1)) * ew, ew, wc);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_kernel(const KParams p, c
             } else {
                 for (int i = lane; i < n; i += 64) sacc = __builtin_fma(lm[i], lm[i], sacc);
             }
-            for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
+            sacc = wave_sum(sacc);
             if (t == mge + 1 && !lamg) sacc *= 0.5;
             if (lane == 0) p.mpart[(item * d + c0 + c) * (m + 2) + (t < mge ? l0 + t : m + (t - mge))] = sacc;
         }

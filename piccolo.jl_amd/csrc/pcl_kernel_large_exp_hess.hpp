@@ -80,16 +80,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_hess_kernel(const KParams
     const double hs = sp > 0 ? h / sp : 0.0;
     // A = G^T (the tile's columns)
     double a[PL_KS];
-    unsigned kmask = 0;
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[kk + LD * row] : 0.0;
-    }
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    unsigned kmask = pl_load_a<true>(G, LD, n, rt, li, lk, a);
     __syncthreads();  // (the norms have been read)
     if (tid < n) B2[tid] = 0.0;
     for (int e = tid; e < nce * n; e += nth) {  // Y = M; the dY and d2Y blocks stay zero
@@ -139,23 +130,13 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_hess_kernel(const KParams
                         const double *w1 = V + LD * (s1 * nc + c);
                         const long long lrow = (long long)l1 * n;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * etw;
-                            double v = 0.0;
-                            for (int e = 0; e < etw; ++e) v = __builtin_fma(p.ellt_val[eb + e], w1[p.ellt_col[eb + e]], v);
-                            y[r] = v;
-                        }
+                        for (int r = 0; r < 4; ++r) y[r] = pl_row_dot(p.ellt_val, p.ellt_col, (lrow + min(r0 + 4 * r, n - 1)) * etw, etw, w1);
                     }
                     if (kind == 2) {
                         const double *w2 = V + LD * (s2 * nc + c);
                         const long long lrow = (long long)l2 * n;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * etw;
-                            double v = y[r];
-                            for (int e = 0; e < etw; ++e) v = __builtin_fma(p.ellt_val[eb + e], w2[p.ellt_col[eb + e]], v);
-                            y[r] = v;
-                        }
+                        for (int r = 0; r < 4; ++r) y[r] = pl_row_dot(p.ellt_val, p.ellt_col, (lrow + min(r0 + 4 * r, n - 1)) * etw, etw, w2, y[r]);  // (onto the first term)
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -201,7 +182,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_exp_hess_kernel(const KParams
     }
     __syncthreads();
     if (diag) {  // G X_k (A = G: the registers are reloaded), behind the nc columns of X_k
-        kmask = lr_load_a(G, LD, n, rt, li, lk, a);
+        kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
         for (int ct = 0; ct < ctz; ++ct) {
             const int vc = ct * 16 + li;
             const bool on = vc < nce;

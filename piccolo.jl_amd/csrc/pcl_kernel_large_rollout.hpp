@@ -32,33 +32,6 @@
 #define LR_THETA 1.0
 #define LR_SMAX 1024
 
-// the wave's 16 rows of the tile, 32 k-steps, and the k-steps with a nonzero among them (wave-uniform)
-__device__ __forceinline__ unsigned lr_load_a(const double *__restrict__ G, int LD, int n, int rt, int li, int lk, double (&a)[PL_KS]) {
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-    }
-    unsigned kmask = 0;
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    return __builtin_amdgcn_readfirstlane(kmask);
-}
-
-// nce columns of n doubles, LDS (leading dimension LD) -> memory (contiguous); pairs where the destination allows it
-__device__ __forceinline__ void lr_store_cols(double *__restrict__ dst, const double *__restrict__ src, int n, int LD, int nce, int tid, int nth) {
-    if (!(n & 1) && !(reinterpret_cast<unsigned long long>(dst) & 15ull)) {
-        const int hn = n >> 1;
-        for (int e = tid; e < nce * hn; e += nth) {
-            const int c = e / hn, i = 2 * (e - c * hn);
-            store2(dst + c * n + i, src[i + LD * c], src[i + 1 + LD * c], 0);
-        }
-    } else {
-        for (int e = tid; e < nce * n; e += nth) dst[e] = src[(e % n) + LD * (e / n)];
-    }
-}
-
 // p.S = panels per interval, p.nc = columns of E per panel, p.lds_doubles = doubles of LDS to zero at the start
 __global__ __launch_bounds__(PL_NT) void pcl_large_expm_kernel(const KParams p) {
     extern __shared__ double lds[];
@@ -90,7 +63,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_expm_kernel(const KParams p) 
     const int sp = x == 0.0 ? 0 : (x <= (double)LR_SMAX * LR_THETA ? (int)ceil(x / LR_THETA) : LR_SMAX);
     const double hs = sp > 0 ? h / sp : 0.0;
     double a[PL_KS];
-    const unsigned kmask = lr_load_a(G, LD, n, rt, li, lk, a);
+    const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     __syncthreads();  // (the norms have been read: the product block is free)
     for (int e = tid; e < npce * n; e += nth) {
         const int c = e / n, i = e - c * n;
@@ -129,10 +102,11 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_expm_kernel(const KParams p) 
         f2 = Y;
         Y = V;
     }
-    lr_store_cols(p.expm + item * (long long)n * n + (long long)pc0 * n, Y, n, LD, npce, tid, nth);
+    pl_store_cols(p.expm + item * (long long)n * n + (long long)pc0 * n, Y, n, LD, npce, tid, nth);
 }
 
-// the same from memory (E: n x n column-major, the workspace, read through L2): 16 consecutive rows per k-step and quarter wave, 128 B each
+// pl_load_a's operand from memory, without the mask (E: n x n column-major, the workspace, read through L2): 16 consecutive rows per k-step
+// and quarter wave, 128 B each
 __device__ __forceinline__ void lr_fetch_a(const double *__restrict__ E, int n, int rt, int li, int lk, double (&a)[PL_KS]) {
 #pragma unroll
     for (int ks = 0; ks < PL_KS; ++ks) {
@@ -189,7 +163,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_large_chain_kernel(const KParams p)
             }
         }
         __syncthreads();  // knot k + 1 is complete in `oth`; nothing reads `cur` any more (the next product writes it)
-        lr_store_cols(out + (long long)(k + 1) * xd, oth, n, LD, nce, tid, nth);
+        pl_store_cols(out + (long long)(k + 1) * xd, oth, n, LD, nce, tid, nth);
         double *t_ = cur;
         cur = oth;
         oth = t_;

@@ -29,30 +29,7 @@
 //   PL_PAYLOAD  delta and those partial sums alone (npc = 0, U = sx ngrp chain units): no panel of the powers, no P' block, no block or tail store.
 #pragma once
 
-#define PL_KS 32     // k-steps of 4 (n <= 128)
-#define PL_NT 512    // most threads per workgroup (8 row tiles)
-#define PL_NP 8      // B^{+-} value pairs per thread (the host keeps n npc / 2 <= PL_NP blockDim)
-#define PL_SLACK 128 // doubles behind the last column block: the B operand loads of a column run 128 rows whatever n is
 enum { PL_FULL = 0, PL_COMPACT = 1, PL_MERIT = 2, PL_PAYLOAD = 3 };
-
-// one 16 x 16 tile of G * B: a[] = this wave's rows of G, Bp = this lane's column of B in LDS + (lane >> 4), kmask = the k-steps with a nonzero
-// in the wave's rows (wave-uniform).  Operand loads are unconditional, base + immediate: every double of the workgroup's LDS is finite
-// (zero-filled at the start), and where k >= n the A operand is an exact zero
-__device__ __forceinline__ double4_t pl_tile(const double (&a)[PL_KS], const double *__restrict__ Bp, unsigned kmask) {
-    // k-step ks into accumulator ks mod 4: four independent chains (a dependent f64 MFMA waits for its accumulator), summed in one fixed order
-    double4_t acc[4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        double b[PL_KS / 2];
-#pragma unroll
-        for (int ks = 0; ks < PL_KS / 2; ++ks) b[ks] = Bp[4 * (ks + half * (PL_KS / 2))];
-#pragma unroll
-        for (int ks = 0; ks < PL_KS / 2; ++ks)
-            if (kmask & (1u << (ks + half * (PL_KS / 2))))
-                acc[ks & 3] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks + half * (PL_KS / 2)], b[ks], acc[ks & 3], 0, 0, 0);
-    }
-    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
-}
 
 // p.S = U units per interval, p.nc state columns per chain unit; sx state-column slices, mg drives per group, npc power columns per unit
 template <bool JAC, int MODE = PL_FULL>
@@ -100,20 +77,11 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
     }
     __syncthreads();
     double a[PL_KS];
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-    }
-    // 16 x 4 blocks of G without a nonzero are skipped (a dispersive qubit-cavity generator has a handful per row tile): adding their
-    // exact-zero products changes nothing but the sign of a zero sum.  The mask depends on G alone, never on the split
-    unsigned kmask = 0;
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     // B^{+-}: each thread owns the flat positions (2 pi, 2 pi + 1), pi = tid + nth r, of the unit's panel (n x npce, contiguous in memory;
-    // in LDS too when n is odd, LD = n; for an even n both positions lie in one column); first terms I + c_1 (+-h) G
+    // in LDS too when n is odd, LD = n; for an even n both positions lie in one column); first terms I + c_1 (+-h) G.  (This loop and the
+    // per-level one below are the same text as pcl_var_large_kernel's on purpose: as shared helpers they cost this kernel's merit instance SGPR
+    // spill reloads and time -- see pcl_device_large.hpp)
     double bp[PL_NP][2], bm[PL_NP][2];
     int o_[PL_NP];
     double hp = h, hm = -h;
@@ -161,12 +129,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
                     const double *wc = Xc + LD * c;
                     const long long lrow = (long long)(l0 + bl - 2) * n;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * ew;
-                        double v = 0.0;
-                        for (int e = 0; e < ew; ++e) v = __builtin_fma(p.ell_val[eb + e], wc[p.ell_col[eb + e]], v);
-                        y[r] = v;
-                    }
+                    for (int r = 0; r < 4; ++r) y[r] = pl_row_dot(p.ell_val, p.ell_col, (lrow + min(r0 + 4 * r, n - 1)) * ew, ew, wc);
                 }
                 double *dst = (isp ? Pn : Xn + bl * LDc) + LD * c;
 #pragma unroll
@@ -221,7 +184,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_kernel(const KParams p, 
             const double *x = Xc + (t < mge ? 2 + t : (t == mge ? 1 : 0)) * LDc + LD * c;
             double sacc = 0.0;
             for (int i = lane; i < n; i += 64) sacc = __builtin_fma(x[i], lamg ? lamg[c * n + i] : Xc[i + LD * c], sacc);
-            for (int off = 32; off > 0; off >>= 1) sacc += __shfl_down(sacc, off, 64);
+            sacc = wave_sum(sacc);
             if (t == mge + 1 && !lamg) sacc *= 0.5;
             if (lane == 0) p.mpart[(item * d + c0 + c) * (m + 2) + (t < mge ? l0 + t : m + (t - mge))] = sacc;
         }

@@ -79,17 +79,8 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_hess_kernel(const KParam
     }
     __syncthreads();
     double a[PL_KS];
-    unsigned kmask = 0;
     // ---- forward chain: A = G -----------------------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-    }
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     const int ctz = (nc + 15) >> 4;
     for (int s = q - 2; s >= 1; --s) {  // Z_s = G Z_{s+1} + T_{s+1} Y_{s+1}
         const double *Ys = ((s + 1) & 1) ? Sm : Dm;
@@ -111,16 +102,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_hess_kernel(const KParam
         __syncthreads();
     }
     // ---- backward chains: A = G^T (the tile's columns) -------------------------------------------------------------------------------------
-    kmask = 0;
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[kk + LD * row] : 0.0;
-    }
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    kmask = pl_load_a<true>(G, LD, n, rt, li, lk, a);
     const int cx = (1 + mg) * nc, ctn = (cx + 15) >> 4;
     const int ew = p.ell_w, etw = p.ellt_w;
     const int i0 = min(lane, n - 1), i1 = min(lane + 64, n - 1);  // the rows a lane takes in the sums (clamped: the loads stay legal)
@@ -152,6 +134,8 @@ __global__ __launch_bounds__(PL_NT) void pcl_pade_large_hess_kernel(const KParam
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int rr = r0 + 4 * r, idx = rr + LD * c;
+                        // pl_row_dot's loop, open here: through the helper the compiler reads the table pointers ahead of the loop guard,
+                        // and this kernel's launches measured slower.  The same operations in the same order
                         const long long eb = (lrow + min(rr, n - 1)) * etw;
                         double y = 0.0;  // (G_l^T W_{s-1})[rr]
                         for (int e = 0; e < etw; ++e) y = __builtin_fma(p.ellt_val[eb + e], wc[p.ellt_col[eb + e]], y);

@@ -4,8 +4,8 @@
 //
 // The one-tile plan of pcl_kernel_pade_large.hpp carries over: the lifted generator var_G(G, [Gv_i]) is block lower triangular with G on the
 // diagonal, so a lifted product is the same matrix-core product  G [columns]  on (1 + v) times as many columns, plus  Gv_b (the column of
-// component 0)  on component b -- a sparse row product read from memory, the shape of the drive term.  pl_tile, PL_KS, PL_NT, PL_NP and PL_SLACK are
-// that file's: one wave per 16-row tile of G with its A operand in registers, fixed k order, four accumulators summed in one order, a wave-uniform
+// component 0)  on component b -- a sparse row product read from memory, the shape of the drive term.  The helpers are those of
+// pcl_device_large.hpp: one wave per 16-row tile of G with its A operand in registers, fixed k order, four accumulators summed in one order, a wave-uniform
 // mask from G alone, zero-filled LDS so that every operand load is unconditional.
 //   - CHAIN unit (interval, state-column slice s of nc columns, drive group g of mg drives): per column and component b = 0 .. v
 //         W_b    <- c_j Y_{b,j} + h (G W_b + [b > 0] Gv_b W_0)             V_b the same with j c_j (the last level without h: d delta / d dt)
@@ -32,13 +32,6 @@ struct VarLargeParams {
     int sx, mg, ngrp;          // chain units: state-column slices, drives per group, groups
     int npc, pu;               // panel units: columns of the powers per unit, units per role
 };
-
-// the Gv_b term of one output element: row `row` of the variation generator against the column x (LDS), in the row's fixed order
-__device__ __forceinline__ double vl_row_dot(const double *__restrict__ val, const int *__restrict__ col, long long eb, int w, const double *x) {
-    double s = 0.0;
-    for (int e = 0; e < w; ++e) s = __builtin_fma(val[eb + e], x[col[eb + e]], s);
-    return s;
-}
 
 // p: Z, delta, jac, G0, upos / ucoef / n_upos (build_G), ell_* (the drives), n, cols, m, K, z_dim, u_off, dt_off, LD, nc, S = units per interval,
 // q, pc, lds_doubles, jac_per, nt -- as launch_pade_large fills them
@@ -84,16 +77,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_kernel(const KParams p, c
         }
         __syncthreads();
         double a[PL_KS];
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks) {
-            const int row = rt * 16 + li, kk = 4 * ks + lk;
-            a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-        }
-        unsigned kmask = 0;  // (as pcl_pade_large_kernel: from G alone, never from the split or from a Gv)
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks)
-            if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-        kmask = __builtin_amdgcn_readfirstlane(kmask);
+        const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);  // (from G alone, never from the split or from a Gv)
         const int cb = T * nc, cx = (1 + v) * cb, ct_n = (cx + 15) >> 4;
         for (int j = q - 1; j >= 0; --j) {
             const double *Yj = (j & 1) ? Sm : Dm;
@@ -116,12 +100,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_kernel(const KParams p, c
                         const double *wc = Xc + b * CB + LD * c;
                         const long long lrow = (long long)(l0 + bl - 2) * n;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const long long eb = (lrow + min(r0 + 4 * r, n - 1)) * ew;
-                            double sv = 0.0;
-                            for (int e = 0; e < ew; ++e) sv = __builtin_fma(p.ell_val[eb + e], wc[p.ell_col[eb + e]], sv);
-                            y[r] = sv;
-                        }
+                        for (int r = 0; r < 4; ++r) y[r] = pl_row_dot(p.ell_val, p.ell_col, (lrow + min(r0 + 4 * r, n - 1)) * ew, ew, wc);
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) t[r] = acc[r];
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_kernel(const KParams p, c
                         const double *x0 = Xc + bl * LDc + LD * c;  // the same block and column of component 0
                         const long long vrow = (long long)(b - 1) * n;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) t[r] = acc[r] + vl_row_dot(w.gv_val, w.gv_col, (vrow + min(r0 + 4 * r, n - 1)) * gw, gw, x0);
+                        for (int r = 0; r < 4; ++r) t[r] = acc[r] + pl_row_dot(w.gv_val, w.gv_col, (vrow + min(r0 + 4 * r, n - 1)) * gw, gw, x0);
                     }
                     double *dst = Xn + b * CB + bl * LDc + LD * c;
 #pragma unroll
@@ -179,16 +158,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_kernel(const KParams p, c
     }
     __syncthreads();
     double a[PL_KS];
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks) {
-        const int row = rt * 16 + li, kk = 4 * ks + lk;
-        a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-    }
-    unsigned kmask = 0;
-#pragma unroll
-    for (int ks = 0; ks < PL_KS; ++ks)
-        if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-    kmask = __builtin_amdgcn_readfirstlane(kmask);
+    const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     // each thread owns the flat positions (2 pi, 2 pi + 1), pi = tid + nth r, of the unit's panel (n x npce, contiguous in memory; n is even: both
     // lie in one column); first terms I + c_1 (+-h) G (role 0), c_1 (+-h) Gv_i (role i)
     double bp[PL_NP][2], bm[PL_NP][2];
@@ -231,7 +201,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_kernel(const KParams p, c
                 for (int r = 0; r < 4; ++r) {
                     const int rr = r0 + 4 * r;
                     double o = acc[r];
-                    if (isq) o = acc[r] + vl_row_dot(w.gv_val, w.gv_col, (vrow + min(rr, n - 1)) * gw, gw, Pc + LD * c);
+                    if (isq) o = acc[r] + pl_row_dot(w.gv_val, w.gv_col, (vrow + min(rr, n - 1)) * gw, gw, Pc + LD * c);
                     if (rr < n) dst[rr] = o;
                 }
             }

@@ -101,17 +101,8 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_hess_kernel(const KParams
             }
         }
         __syncthreads();
-        unsigned kmask = 0;
         // ---- forward chain of this pass's component: A = G ------------------------------------------------------------------------------------
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks) {
-            const int row = rt * 16 + li, kk = 4 * ks + lk;
-            a[ks] = (row < n && kk < n) ? G[row + LD * kk] : 0.0;
-        }
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks)
-            if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-        kmask = __builtin_amdgcn_readfirstlane(kmask);
+        unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
         const int ctz = (nc + 15) >> 4;
         for (int s = q - 2; s >= 1; --s) {  // Z_s = G Z_{s+1} + [b > 0] Gv_b Z_{0,s+1} + T_{s+1} Y_{s+1}
             const double *Ys = ((s + 1) & 1) ? Sm : Dm;
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_hess_kernel(const KParams
                     for (int r = 0; r < 4; ++r) {
                         const int rr = rt * 16 + lk + 4 * r;
                         double t = acc[r];
-                        if (b) t = acc[r] + vl_row_dot(w.gv_val, w.gv_col, ((long long)(b - 1) * n + min(rr, n - 1)) * gw, gw, Z0 + s * LDc + LD * c);
+                        if (b) t = acc[r] + pl_row_dot(w.gv_val, w.gv_col, ((long long)(b - 1) * n + min(rr, n - 1)) * gw, gw, Z0 + s * LDc + LD * c);
                         if (rr < n) dst[rr + LD * c] = __builtin_fma(Ts, Ys[rr + LD * c], t);
                     }
                 }
@@ -135,16 +126,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_hess_kernel(const KParams
             __syncthreads();
         }
         // ---- backward chains: A = G^T (the tile's columns) -------------------------------------------------------------------------------------
-        kmask = 0;
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks) {
-            const int row = rt * 16 + li, kk = 4 * ks + lk;
-            a[ks] = (row < n && kk < n) ? G[kk + LD * row] : 0.0;
-        }
-#pragma unroll
-        for (int ks = 0; ks < PL_KS; ++ks)
-            if (__ballot(a[ks] != 0.0)) kmask |= 1u << ks;
-        kmask = __builtin_amdgcn_readfirstlane(kmask);
+        kmask = pl_load_a<true>(G, LD, n, rt, li, lk, a);
         const int cb = (1 + mg) * nc, cx = ncomp * cb, ctn = (cx + 15) >> 4;
         const long long trow = (long long)(b - 1) * n;  // Gv_b^T's rows (b > 0)
         for (int s = 1; s <= q; ++s) {
@@ -166,7 +148,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_hess_kernel(const KParams
                         for (int r = 0; r < 4; ++r) {
                             const int rr = r0 + 4 * r, idx = rr + LD * c;
                             double t = acc[r];
-                            if (fed) t = acc[r] + vl_row_dot(w.gvt_val, w.gvt_col, (trow + min(rr, n - 1)) * gtw, gtw, xb);
+                            if (fed) t = acc[r] + pl_row_dot(w.gvt_val, w.gvt_col, (trow + min(rr, n - 1)) * gtw, gtw, xb);
                             if (rr < n) {
                                 Xo[idx] = t;
                                 A4[idx] = __builtin_fma(T1, t, A4[idx]);
@@ -180,11 +162,9 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_hess_kernel(const KParams
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int rr = r0 + 4 * r, idx = rr + LD * c;
-                            const long long eb = (lrow + min(rr, n - 1)) * etw;
-                            double y = 0.0;  // (G_l^T W_{s-1})[rr]
-                            for (int e = 0; e < etw; ++e) y = __builtin_fma(p.ellt_val[eb + e], wc[p.ellt_col[eb + e]], y);
+                            const double y = pl_row_dot(p.ellt_val, p.ellt_col, (lrow + min(rr, n - 1)) * etw, etw, wc);  // (G_l^T W_{s-1})[rr]
                             double vv = acc[r] + y;
-                            if (fed) vv = vv + vl_row_dot(w.gvt_val, w.gvt_col, (trow + min(rr, n - 1)) * gtw, gtw, xb);
+                            if (fed) vv = vv + pl_row_dot(w.gvt_val, w.gvt_col, (trow + min(rr, n - 1)) * gtw, gtw, xb);
                             if (rr < n) {
                                 Xo[bl * LDc + idx] = vv;
                                 A3[t * LDc + idx] = __builtin_fma(Ts, vv, A3[t * LDc + idx]);

@@ -1,8 +1,8 @@
 // Rollout of the stacked state on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, 66 <= n <= 128; option
 // large_var_full): from the knot-0 state,  x <- E x,  x_i <- E x_i + L_i x  per knot, E = exp(h G(u_k)), L_i the Frechet derivative of exp at h G
 // along h Gv_i; output [N][(1 + v) n cols] -- the contract of pcl_var_expm_kernel + pcl_var_chain_kernel (pcl_kernel_var_rollout.hpp).  Those hold
-// four or five n x n tiles; here ONE fits, so this is the two-launch plan of pcl_kernel_large_rollout.hpp with its helpers (pl_tile, lr_load_a,
-// lr_fetch_a, lr_store_cols, LR_DEG, LR_THETA, LR_SMAX), and the lifted (1 + v) n square matrix is never formed.
+// four or five n x n tiles; here ONE fits, so this is the two-launch plan of pcl_kernel_large_rollout.hpp with its helpers (lr_fetch_a, LR_DEG, LR_THETA,
+// LR_SMAX) and those of pcl_device_large.hpp, and the lifted (1 + v) n square matrix is never formed.
 //
 //   pcl_var_large_expm_kernel   one workgroup per (interval, role, panel of npc columns).  Role 0 is E: the operations of pcl_large_expm_kernel in
 //       its order (the bits of a plain PCL_LARGE_N context on the same drift and drives).  Role i = 1 .. v carries V again, with the same
@@ -10,7 +10,7 @@
 //           Vv <- Yv + f (G Vv + Gv_i V)        (the V before this level's update)
 //           V  <- Y  + f G V
 //       then Y <- V, Yv <- Vv; start Y = I[:, panel], Yv = 0.  G Vv and G V are ONE pass of matrix-core column tiles over the 2 npc columns of the
-//       pair, the wave's rows of G in registers; Gv_i V is the row-compressed Gv_i against the old column of V in LDS (vl_row_dot, the row's fixed
+//       pair, the wave's rows of G in registers; Gv_i V is the row-compressed Gv_i against the old column of V in LDS (pl_row_dot, the row's fixed
 //       order).  s' = ceil(|h| |G|_1) comes from the tile of G alone, clamped at LR_SMAX: every role and panel of an interval takes the same
 //       substeps.  h = 0: s' = 0, E = I and L_i = 0 exactly; a negative h is an ordinary step.
 //       LDS (doubles): G | three pairs [V | Vv] of npc columns each (Y, and the two the levels alternate between) | slack | us.
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_expm_kernel(const KParams
     const int sp = x == 0.0 ? 0 : (x <= (double)LR_SMAX * LR_THETA ? (int)ceil(x / LR_THETA) : LR_SMAX);
     const double hs = sp > 0 ? h / sp : 0.0;
     double a[PL_KS];
-    const unsigned kmask = lr_load_a(G, LD, n, rt, li, lk, a);
+    const unsigned kmask = pl_load_a<false>(G, LD, n, rt, li, lk, a);
     __syncthreads();  // (the norms have been read: the last pair is free)
     for (int e = tid; e < npce * n; e += nth) {
         const int c = e / n, i = e - c * n;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_expm_kernel(const KParams
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int rr = r0 + 4 * r;
-                            const double t = acc[r] + vl_row_dot(w.gv_val, w.gv_col, (vrow + min(rr, n - 1)) * gw, gw, V + LD * c);
+                            const double t = acc[r] + pl_row_dot(w.gv_val, w.gv_col, (vrow + min(rr, n - 1)) * gw, gw, V + LD * c);
                             if (rr < n) D[rr + LD * vc] = __builtin_fma(f, t, Y[rr + LD * vc]);
                         }
                     }
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_expm_kernel(const KParams
         Y = V;
     }
     const long long nn = (long long)n * n;
-    lr_store_cols(p.expm + (k * (1 + v) + role) * nn + (long long)pc0 * n, role ? Y + LD * npc : Y, n, LD, npce, tid, nth);
+    pl_store_cols(p.expm + (k * (1 + v) + role) * nn + (long long)pc0 * n, role ? Y + LD * npc : Y, n, LD, npce, tid, nth);
 }
 
 // lr_fetch_a on one base pointer per lane (its row, its first k) and one stride: the operand's 32 addresses are then immediates of one register pair
@@ -202,8 +202,8 @@ __global__ __launch_bounds__(PL_NT) void pcl_var_large_chain_kernel(const KParam
             }
         }
         __syncthreads();  // knot k + 1 is complete in `oth`; nothing reads `cur` any more (the next products write it)
-        if (first) lr_store_cols(out0 + (long long)(k + 1) * xd, oth, n, LD, nce, tid, nth);
-        lr_store_cols(outv + (long long)(k + 1) * xd, oth + LD * nc, n, LD, nce, tid, nth);
+        if (first) pl_store_cols(out0 + (long long)(k + 1) * xd, oth, n, LD, nce, tid, nth);
+        pl_store_cols(outv + (long long)(k + 1) * xd, oth + LD * nc, n, LD, nce, tid, nth);
         double *t_ = cur;
         cur = oth;
         oth = t_;

@@ -5,6 +5,7 @@
 //   pcl_kernels_fused_v2.hpp   fallback (two workgroups per CU); also kets and the compact Jacobian at large n
 //   pcl_kernels_reference.hpp  single-role kernel (A/B reference) and the general-order kernel (Pade 2..10)
 //   pcl_kernel_eval.hpp        residual only (pcl_eval): persistent, three barriers per interval
+//   pcl_device_large.hpp       what the kernels of generator dimensions 66 .. 128 share: the one-tile MFMA product, the A operand and its mask, the sparse row product, the panel registers, the column store
 //   pcl_kernel_pade_large.hpp  generator dimensions 66 .. 128 (contexts created with PCL_LARGE_N): one LDS tile, the powers of G by column panels, the drives in groups
 //   pcl_kernel_large_exp_hess.hpp   ... its Hessian of the Lagrangian (option large_exp_hess): the adjoint of that recurrence with the second derivative carried, per-column partial sums
 //   pcl_kernel_var_large.hpp        ... the variational integrators there (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR): chain units of 1 + v components, panel units of the powers and, one variation at a time, the Frechet powers
@@ -56,6 +57,7 @@
 #include "pcl_device_common.hpp"
 #include "pcl_kernels_reference.hpp"
 #include "pcl_kernel_pade_v2.hpp"
+#include "pcl_device_large.hpp"
 #include "pcl_kernel_pade_large.hpp"
 #include "pcl_kernel_pade_large_hess.hpp"
 #include "pcl_kernel_large_rollout.hpp"
@@ -1270,16 +1272,14 @@ extern "C" int pcl_hess_dev(pcl_ctx *ctx, const double *Z, const double *mu, dou
 // workspace into registers).  The widest panel that fits is evened over the panels; launches of few intervals take up to one panel per 16
 // columns while the grid stays within one round of the CUs (option general_slices: that many panels at least).  The chain takes slices of at most 16 state columns, one matrix-core column tile (option
 // cols_per_slice: that many at most), evened.  One column always fits (n = 128, m = 24: 136,472 B and 3,088 B).  Every split gives the same bits.
-struct LargeRollPlan {
-    int LD, threads, P, npc, S, nc;
+struct LargeRollPlan : LargeTile {
+    int P, npc, S, nc;
     size_t lds_e, lds_c;
 };
 static void large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, long long items, LargeRollPlan &R) {
-    R.LD = n | 1;
-    R.threads = 64 * ((n + 15) / 16);
-    const long long budget = ctx->max_lds / (long long)sizeof(double), tile = (long long)R.LD * n;
-    const long long fixed_e = tile + PL_SLACK + m + 8, fixed_c = PL_SLACK;
-    const int npc_max = (int)std::max<long long>(1, std::min<long long>(n, (budget - fixed_e) / R.LD / 3));
+    static_cast<LargeTile &>(R) = large_tile(ctx->max_lds, n, m);  // (the propagator launch's; the chain launch has the slack alone.  NB >= 0: the tile fits for n <= 128)
+    const long long budget = ctx->max_lds / (long long)sizeof(double), fixed_c = PL_SLACK;
+    const int npc_max = std::max(1, std::min(n, R.NB / 3));
     const int p_min = (n + npc_max - 1) / npc_max;
     const long long want = ctx->opt_general_slices > 0 ? ctx->opt_general_slices : std::min<long long>((n + 15) / 16, ctx->n_cu / std::max(items, 1LL));
     R.P = (int)std::max<long long>(p_min, std::min<long long>(want, n));
@@ -1288,9 +1288,8 @@ static void large_roll_plan(const pcl_ctx *ctx, int n, int cols, int m, long lon
     const int nc_fit = (int)std::max<long long>(1, (budget - fixed_c) / R.LD / 2);
     const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16);
     R.nc = std::min(nc_cap, nc_fit);
-    R.S = (cols + R.nc - 1) / R.nc;
-    R.nc = (cols + R.S - 1) / R.S;  // even slices
-    R.lds_e = (size_t)(fixed_e + 3LL * R.LD * R.npc) * sizeof(double);
+    R.S = even_split(cols, R.nc);  // even slices
+    R.lds_e = (size_t)(R.fixed + 3LL * R.LD * R.npc) * sizeof(double);
     R.lds_c = (size_t)(fixed_c + 2LL * R.LD * R.nc) * sizeof(double);
 }
 static int launch_large_rollout(pcl_ctx *ctx, const double *Z, double *X_out) {

@@ -199,7 +199,7 @@ def test_constants_and_header():
     assert "#define PCL_MAX_D 32" in text and "#define PCL_LARGE_MAX_N 128" in text
     src = open(L.CSRC + "/pcl_kernel_variational.hpp").read()
     assert "#define PCL_VAR_MAXV 2 " in src
-    large = open(L.CSRC + "/pcl_kernel_pade_large.hpp").read()
+    large = open(L.CSRC + "/pcl_device_large.hpp").read()
     assert "#define PL_NP %d " % vl.NP_PAIRS in large and "#define PL_SLACK %d " % vl.SLACK in large
 
 
