@@ -345,6 +345,36 @@ typedef enum pcl_status {
  * "large_hess" on the same drift and drives.  The other refusals above stay at either value. */
 #define PCL_LARGE_VAR 0x400
 
+/* A fourth pcl_desc.batch_mode flag: the variational integrators on the EXACT exponential constraint (PCL_BATCH_VARIATIONAL_EXP, the reference's
+ * own BilinearIntegrator(var_G(G(u), [Gv_i]))) at generator dimensions 66 .. 128.  Valid in ONE combination only,
+ *     PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP   with   pade_order = PCL_ORDER_EXP;
+ * chosen at creation only, pcl_create strips it with the others.  Every descriptor WITHOUT this flag behaves exactly as before (PCL_LARGE_VAR
+ * with PCL_BATCH_VARIATIONAL_EXP, PCL_LARGE_EXP or PCL_ORDER_EXP keeps its PCL_ENOTIMPL).  With it, each PCL_EINVAL naming what is missing,
+ * before the device is touched:
+ *   without PCL_LARGE_N or PCL_LARGE_VAR; with PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ or PCL_BATCH_VARIATIONAL;
+ *   with a Pade order (or order 0); with PCL_LARGE_EXP (that flag belongs to plain contexts)                          PCL_EINVAL
+ *   all four flags, n <= 64                        the ordinary PCL_BATCH_VARIATIONAL_EXP context: same kernels, same bits (n = 64: its PCL_ESHAPE)
+ *   66 <= n <= 128, v = 1 or 2, m <= 24, state_cols d, 1 or any count of kets between              a LARGE VARIATIONAL EXPONENTIAL context
+ *   n > 128                                                                                         PCL_ESHAPE with the byte counts, as for PCL_LARGE_VAR
+ * Rows, value order, layout, structure, pcl_constraint_dim, pcl_jac_nnz and index_base are exactly those of PCL_BATCH_VARIATIONAL_EXP at
+ * n <= 62: (1 + 2v) C n^2 + x_dim' (m + 2) values per interval, no structural zeros.  One kernel (pcl_kernel_var_large_exp.hpp):
+ * the substepped degree-18 Taylor polynomial in action form on the lifted pair [V | Vv_i] with the drive derivative carried through it,
+ * s' = ceil(|h| |G(u_k)|_1) substeps.  No atomics: every work split, two launches, both pointer paths and the residual-only launch against the
+ * fused launch's residual give the same bits; component 0 (delta_0, every copy of -E, its tails) has the bits of a plain
+ * PCL_LARGE_N | PCL_LARGE_EXP context of the same drift and drives.  h = 0 gives E = I, L_i = 0 and zero drive tails exactly.
+ * Served: pcl_create / pcl_destroy, pcl_constraint_dim, pcl_jac_nnz, pcl_jac_structure[_i64], pcl_eval[_dev], pcl_jac[_dev], pcl_eval_jac[_dev]
+ * (host-pointer calls deliver full values), streams and sync, options, and by option "large_var_full" = 1 the objective family and
+ * pcl_rollout[_dev] through the kernels of a large variational context (the same bits: neither depends on the constraint; the rollout then has
+ * the discretisation of the rows).  pcl_set_order_policy / pcl_set_order_from_trajectory: PCL_EINVAL, as on every exponential context.
+ * PCL_ENOTIMPL, each message naming PCL_LARGE_VAR_EXP: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64], the compact trio, the merit /
+ * reduce / step entry points, the collective and the member window, pcl_infidelity_dev, and the options "large_var_hess", "var_compact",
+ * "var_exp_hess", "var_full" and "exp_hess" = 1.  The other large options = 1 are PCL_EINVAL, as on every context that is not of their kind.
+ * Options: "cols_per_slice" caps the state columns per chain workgroup, "general_slices" sets the least number of panel workgroups,
+ * "large_var_exp_drives" caps the drives per chain workgroup (0 auto; PCL_EINVAL when negative or off such a context); get_option
+ * "large_variational_exp" reads 1, "large_variational" 1, "last_kernel" 370 after a residual + Jacobian launch and 371 after a residual-only
+ * launch (360 after the rollout).  "jit_compiles" stays 0: the kernel is part of the library. */
+#define PCL_LARGE_VAR_EXP 0x800
+
 typedef struct pcl_desc {
     int32_t struct_size; /* = sizeof(pcl_desc) (ABI check) */
     int32_t d;           /* Hilbert-space dimension (sys.levels); n = 2d, x_dim = 2 d^2 */

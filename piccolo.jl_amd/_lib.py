@@ -21,6 +21,7 @@ PCL_BATCH_VARIATIONAL_EXP = 3  # the variational integrators on the exponential 
 PCL_LARGE_N = 0x100  # pcl_desc.batch_mode flag (with PCL_BATCH_MEMBERS / PCL_BATCH_TRAJ): generator dimensions 66 .. 128 on the Pade constraint: residual and Jacobian, the Hessian of the Lagrangian by option large_hess
 PCL_LARGE_EXP = 0x200  # a second flag beside PCL_LARGE_N: the exponential constraint (pade_order "exp") at generator dimensions 66 .. 128: residual and Jacobian
 PCL_LARGE_VAR = 0x400  # a third flag beside PCL_LARGE_N: the variational integrators (PCL_BATCH_VARIATIONAL, Pade constraint) at generator dimensions 66 .. 128: residual and Jacobian
+PCL_LARGE_VAR_EXP = 0x800  # a fourth flag, with PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR and pade_order "exp" only: the variational exponential constraint at generator dimensions 66 .. 128: residual and Jacobian
 PCL_STATE_VECTOR = -1  # pcl_desc.state_cols: general real d x d generator on one real column (compact density vectors)
 PCL_ORDER_EXP = -1  # pcl_desc.pade_order: the exact exponential constraint delta_k = X_{k+1} - exp(dt_k G(u_k)) X_k (its Hessian of the Lagrangian by option exp_hess only)
 _STATUS_NAMES = {0: "PCL_OK", -1: "PCL_EINVAL", -2: "PCL_ENOMEM", -3: "PCL_EHIP", -4: "PCL_ERCCL", -5: "PCL_ESHAPE", -6: "PCL_ENOTIMPL", -7: "PCL_EINTERNAL"}

@@ -134,6 +134,9 @@ static const OptRow kOptions[] = {
             "%s must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)", &pcl_ctx::large_var),
     opt_row("large_var_hess_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_var_hess_drives, 0, OPT_MAX, 0, 0,
             "%s must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)", &pcl_ctx::large_var),
+    opt_row("large_var_exp_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_var_exp_drives, 0, OPT_MAX, 0, 0,
+            "%s must be >= 0, on a large variational exponential context (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, generator dimension above 64)", &pcl_ctx::large_var_exp),
+    read_only("large_variational_exp", OPT_READ(c->large_var_exp)),  // 1: a large variational exponential context (the four flags at a generator dimension above 64)
     read_only("large_variational", OPT_READ(c->large_var)),  // 1: a large variational context (PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64)
     opt_row("large_hess_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_hess_drives, 0, OPT_MAX, 0, 0, "%s must be >= 0, on a large context (PCL_LARGE_N, generator dimension above 64)", &pcl_ctx::large),
     opt_row("large_exp_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_exp_drives, 0, OPT_MAX, 0, 0,

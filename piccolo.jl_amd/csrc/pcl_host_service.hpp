@@ -3,10 +3,10 @@
 // launch ladders (serves) and by the setters of the gate options (set_gate).  DESIGN.md prints the table ("Context kinds and what they serve").
 #pragma once
 
-// The seven kinds of context: what pcl_create made of batch_mode, its flags and pade_order.  A context is of exactly one.
-enum Kind { KIND_PLAIN, KIND_EXP, KIND_VAR, KIND_VAR_EXP, KIND_LARGE, KIND_LARGE_EXP, KIND_LARGE_VAR, N_KINDS };
+// The eight kinds of context: what pcl_create made of batch_mode, its flags and pade_order.  A context is of exactly one.
+enum Kind { KIND_PLAIN, KIND_EXP, KIND_VAR, KIND_VAR_EXP, KIND_LARGE, KIND_LARGE_EXP, KIND_LARGE_VAR, KIND_LARGE_VAR_EXP, N_KINDS };
 static Kind kind_of(const pcl_ctx *c) {
-    return c->large_var ? KIND_LARGE_VAR : c->large_exp ? KIND_LARGE_EXP : c->large ? KIND_LARGE : c->vexp ? KIND_VAR_EXP : c->var ? KIND_VAR : c->exp ? KIND_EXP : KIND_PLAIN;
+    return c->large_var_exp ? KIND_LARGE_VAR_EXP : c->large_var ? KIND_LARGE_VAR : c->large_exp ? KIND_LARGE_EXP : c->large ? KIND_LARGE : c->vexp ? KIND_VAR_EXP : c->var ? KIND_VAR : c->exp ? KIND_EXP : KIND_PLAIN;
 }
 
 // The families of entry points a kind serves, refuses or serves by option (the residual and the Jacobian are served by every kind).
@@ -44,12 +44,12 @@ struct GateInfo {
 };
 static const GateInfo kGates[N_GATES] = {
     {nullptr, 0, nullptr, FEAT_HESS, nullptr},
-    {&pcl_ctx::exp_hess, KIND_BIT(KIND_LARGE_EXP) | KIND_BIT(KIND_VAR_EXP), "%s = 1 needs a context of the exponential constraint (PCL_ORDER_EXP)", FEAT_HESS,
+    {&pcl_ctx::exp_hess, KIND_BIT(KIND_LARGE_EXP) | KIND_BIT(KIND_VAR_EXP) | KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a context of the exponential constraint (PCL_ORDER_EXP)", FEAT_HESS,
      [](pcl_ctx *c, int64_t on) { return on ? exp_hess_fits(c, "exp_hess = 1") : PCL_OK; }},
     {&pcl_ctx::exp_full, KIND_BIT(KIND_LARGE_EXP), "%s = 1 needs a plain context of the exponential constraint (PCL_ORDER_EXP, not a variational one)", FEAT_COMPACT, nullptr},
-    {&pcl_ctx::var_full, KIND_BIT(KIND_LARGE_VAR), "%s = 1 needs a variational context (PCL_BATCH_VARIATIONAL)", FEAT_OBJECTIVE, var_set_full},
-    {&pcl_ctx::var_compact, KIND_BIT(KIND_LARGE_VAR), "%s = 1 needs a variational context (PCL_BATCH_VARIATIONAL or PCL_BATCH_VARIATIONAL_EXP)", FEAT_COMPACT, nullptr},
-    {&pcl_ctx::var_exp_hess, 0, "%s = 1 needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)", FEAT_HESS,
+    {&pcl_ctx::var_full, KIND_BIT(KIND_LARGE_VAR) | KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a variational context (PCL_BATCH_VARIATIONAL)", FEAT_OBJECTIVE, var_set_full},
+    {&pcl_ctx::var_compact, KIND_BIT(KIND_LARGE_VAR) | KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a variational context (PCL_BATCH_VARIATIONAL or PCL_BATCH_VARIATIONAL_EXP)", FEAT_COMPACT, nullptr},
+    {&pcl_ctx::var_exp_hess, KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a variational context of the exponential constraint (PCL_BATCH_VARIATIONAL_EXP)", FEAT_HESS,
      [](pcl_ctx *c, int64_t on) { return on ? var_exp_hess_enable(c) : PCL_OK; }},
     {&pcl_ctx::large_hess, KIND_BIT(KIND_LARGE_EXP), "%s = 1 needs a large context (batch_mode | PCL_LARGE_N at a generator dimension above 64); every other context has its Hessian options of its own", FEAT_HESS,
      [](pcl_ctx *c, int64_t on) { return on ? large_hess_enable(c) : PCL_OK; }},
@@ -63,7 +63,7 @@ static const GateInfo kGates[N_GATES] = {
      nullptr},
     {&pcl_ctx::large_var_full, 0, "%s = 1 needs a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64); every other context serves its objective and rollout without it or by an option of its own", FEAT_OBJECTIVE,
      var_large_set_full},
-    {&pcl_ctx::large_var_hess, 0, "%s = 1 needs a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64); every other context has its Hessian options of its own", FEAT_HESS,
+    {&pcl_ctx::large_var_hess, KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64); every other context has its Hessian options of its own", FEAT_HESS,
      [](pcl_ctx *c, int64_t on) { return on ? var_large_hess_enable(c) : PCL_OK; }},
 };
 
@@ -86,6 +86,7 @@ static const Cell kService[N_KINDS][N_FEATURES] = {
     /* LARGE     */ {{GATE_LARGE_HESS},                         {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE, GATE_LARGE_FULL},     ALWAYS},
     /* LARGE_EXP */ {{GATE_LARGE_EXP_HESS},                     {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE, GATE_LARGE_FULL}, ALWAYS},
     /* LARGE_VAR */ {{GATE_LARGE_VAR_HESS},                     {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
+    /* LARGE_VAR_EXP */ {NEVER,                                 {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
 };
 
 static bool serves(const pcl_ctx *ctx, Feature f) {
@@ -106,6 +107,8 @@ static int refuse(const pcl_ctx *ctx, Feature f, const char *what, bool from_set
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a context created with PCL_LARGE_N (generator dimension %d > 64): residual and Jacobian only", what, ctx->n);
         case KIND_LARGE_VAR:
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension %d > 64): residual and Jacobian only", what, ctx->n);
+        case KIND_LARGE_VAR_EXP:
+            return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a large variational exponential context (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, generator dimension %d > 64): residual and Jacobian, and by option large_var_full the objective and the rollout", what, ctx->n);
         case KIND_VAR:
         case KIND_VAR_EXP:
             return fail(ctx, PCL_ENOTIMPL, "%s is not implemented for a variational context (%s)", what, ctx->vexp ? "PCL_BATCH_VARIATIONAL_EXP" : "PCL_BATCH_VARIATIONAL");

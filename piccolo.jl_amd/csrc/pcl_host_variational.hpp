@@ -10,6 +10,7 @@
 #include "pcl_kernel_var_large.hpp"
 #include "pcl_kernel_var_large_hess.hpp"
 #include "pcl_kernel_var_large_rollout.hpp"
+#include "pcl_kernel_var_large_exp.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).
@@ -20,7 +21,7 @@ static long long var_jac_per(const pcl_ctx *c) {
 
 // Validation of a variational descriptor: every check runs before any device call; the message names the field.
 // large_var: the descriptor carried PCL_LARGE_N | PCL_LARGE_VAR (generator dimensions up to PCL_LARGE_MAX_N on the Pade constraint)
-static int var_validate(const pcl_desc *D, bool large_var) {
+static int var_validate(const pcl_desc *D, bool large_var) {  // (PCL_LARGE_VAR_EXP: the same limits)
     const int d = D->d, m = D->n_drives;
     if (D->batch < 2) return fail(nullptr, PCL_EINVAL, "pcl_create: batch=%d; PCL_BATCH_VARIATIONAL takes batch = 1 + v with v >= 1 variations", D->batch);
     if (D->per_member_G0 != 1)
@@ -78,7 +79,7 @@ static size_t var_exp_lds_bytes(int n, size_t max_lds, int *g_lds) {
     return six ? five + tile : five;
 }
 
-static int var_create(const pcl_desc *dsc, pcl_ctx **out, bool large_var_flag = false) {
+static int var_create(const pcl_desc *dsc, pcl_ctx **out, bool large_var_flag = false, bool large_var_exp_flag = false) {
     if (int rc = var_validate(dsc, large_var_flag)) return rc;
     const int d = dsc->d, m = dsc->n_drives, n = 2 * d, v = dsc->batch - 1;
     const int cols = dsc->state_cols > 0 ? dsc->state_cols : d;
@@ -94,6 +95,7 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out, bool large_var_flag = 
     ctx->var = v;
     ctx->vexp = dsc->batch_mode == PCL_BATCH_VARIATIONAL_EXP ? 1 : 0;
     ctx->large_var = large_var_flag && n > 2 * PCL_MAX_D ? 1 : 0;  // (the flags at n <= 64: the ordinary variational context)
+    ctx->large_var_exp = ctx->large_var && large_var_exp_flag ? 1 : 0;
     ctx->n = n;
     ctx->K = dsc->N - 1;
     ctx->cols = cols;
@@ -150,7 +152,7 @@ static int var_create(const pcl_desc *dsc, pcl_ctx **out, bool large_var_flag = 
     }
     ctx->max_lds = (int)prop.maxSharedMemoryPerMultiProcessor;
     ctx->n_cu = prop.multiProcessorCount;
-    if (ctx->vexp && var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr) > (size_t)ctx->max_lds) {
+    if (ctx->vexp && !ctx->large_var_exp && var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr) > (size_t)ctx->max_lds) {
         fail(nullptr, PCL_ESHAPE, "pcl_create: PCL_BATCH_VARIATIONAL_EXP needs %zu B of LDS (> %d) for n=%d: five n x n tiles of %zu B (served up to n = 62)",
              var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr), ctx->max_lds, n, var_exp_lds_bytes(n, (size_t)ctx->max_lds, nullptr) / 5);
         pcl_destroy(ctx);
@@ -707,8 +709,115 @@ static int var_large_launch(pcl_ctx *ctx, const double *Z, double *delta, double
     return PCL_OK;
 }
 
+// Large variational exponential kernel (pcl_kernel_var_large_exp.hpp; contexts created with PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR |
+// PCL_LARGE_VAR_EXP).  The plan: LD = n | 1, 64 threads per 16-row tile of G; what the one tile leaves of the LDS is NB column blocks of LD doubles,
+// a third of them (NBW) per buffer, since Y, V and the level's result rotate through three.  A chain unit takes nc state columns (at most 16; option
+// cols_per_slice sets another cap) and mg drives (option large_var_exp_drives caps them) of ALL 1 + v components: (1 + v) nc (1 + mg) columns,
+// (1 + v) nc without the Jacobian.  Every group forms the value slot again, and a matrix-core pass costs the same for 1 .. 16 columns, so among
+// the (nc, mg) that fit -- slices and groups evened -- the pair with the fewest 16-column passes per interval, sx ngrp ceil(columns / 16), is taken;
+// on a tie the fewest units, then the wider slice.  A panel unit takes npc columns of the identity for all components, (1 + v) npc columns: the
+// most that fit one pass (16 / (1 + v)) and a buffer; option general_slices: that many panel units at least.  Every split gives the same bits.
+struct VarLargeExpPlan : LargeTile {
+    int NBW, sx, nc, mg, ngrp, chain_units, npc, pu, U, W;
+    long long passes;  // 16-column passes per interval and level: what the launch costs
+    size_t lds;
+};
+static void var_large_exp_plan(const pcl_ctx *ctx, int n, int cols, int m, int v, bool jac, VarLargeExpPlan &P) {
+    const int comp = 1 + v;
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
+    P.NBW = P.NB / 3;
+    const bool drv = jac && m > 0;
+    const int nc_cap = ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16);
+    const int mg_cap = drv ? (ctx->opt_large_var_exp_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_var_exp_drives, m) : m) : 0;
+    // (nothing fits: one column, one drive -- the launch then refuses by its byte count)
+    P.nc = 1, P.mg = drv ? 1 : 0, P.ngrp = drv ? m : 1, P.sx = cols;
+    long long best = -1, best_u = -1;
+    for (int nc0 = nc_cap; nc0 >= 1; --nc0)
+        for (int mg0 = mg_cap; mg0 >= (drv ? 1 : 0); --mg0) {
+            int nc = nc0, mg = mg0;
+            const int sx = even_split(cols, nc), ngrp = drv ? even_split(m, mg) : 1;
+            const int cx = comp * nc * (1 + mg);
+            if (cx > P.NBW) continue;
+            const long long units = (long long)sx * ngrp, cost = units * ((cx + 15) / 16);
+            if (best < 0 || cost < best || (cost == best && units < best_u)) best = cost, best_u = units, P.nc = nc, P.mg = mg, P.sx = sx, P.ngrp = ngrp;
+        }
+    P.chain_units = P.sx * P.ngrp;
+    P.npc = P.pu = 0;
+    if (jac) {
+        const int npc_fit = std::max(1, std::min(n, std::min(P.NBW, 16) / comp));
+        P.pu = (n + npc_fit - 1) / npc_fit;
+        if (ctx->opt_general_slices > 0) P.pu = (int)std::max<long long>(P.pu, std::min<long long>(ctx->opt_general_slices, n));
+        P.npc = (n + P.pu - 1) / P.pu;
+        P.pu = (n + P.npc - 1) / P.npc;  // (no unit without work)
+    }
+    P.U = P.chain_units + P.pu;
+    const int cx = comp * P.nc * (1 + P.mg);
+    P.W = std::max(cx, comp * P.npc);
+    P.passes = (long long)P.chain_units * ((cx + 15) / 16) + (long long)P.pu * ((comp * P.npc + 15) / 16);
+    P.lds = (size_t)(P.fixed + 3LL * P.LD * P.W) * sizeof(double);
+}
+static int var_large_exp_launch(pcl_ctx *ctx, const double *Z, double *delta, double *vals) {
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var;
+    const bool jac = vals != nullptr;
+    VarLargeExpPlan P;
+    var_large_exp_plan(ctx, n, ctx->cols, m, v, jac, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large variational exponential kernel needs %zu B of LDS (> %d) for n = %d, m = %d, v = %d", P.lds, ctx->max_lds, n, m, v);
+    KParams p;
+    memset(&p, 0, sizeof p);
+    p.Z = Z;
+    p.delta = delta;
+    p.jac = vals;
+    p.G0 = ctx->dvar_tab;  // (build_G as var_large_launch sets it up: the drift, and the drives on the union table)
+    p.upos = ctx->dupos;
+    p.ucoef = ctx->ducoef;
+    p.n_upos = ctx->n_upos;
+    p.ell_val = ctx->dell_val;
+    p.ell_col = ctx->dell_col;
+    p.ell_w = ctx->ell_w;
+    p.x_off0 = -1;
+    p.jac_per = var_jac_per(ctx);
+    p.d = D.d;
+    p.n = n;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.batch = 1;
+    p.cols = ctx->cols;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.LD = P.LD;
+    p.nt = ctx->opt_nt == 1 ? 1 : 0;  // (plain or nontemporal block stores)
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    VarLargeParams w;
+    memset(&w, 0, sizeof w);
+    w.gv_val = ctx->dvl_gval;
+    w.gv_col = ctx->dvl_gcol;
+    w.gv_w = ctx->vl_gw;
+    w.v = v;
+    for (int b = 0; b <= v; ++b) w.xo[b] = ctx->x_offs[b];
+    w.sx = P.sx;
+    w.mg = P.mg;
+    w.ngrp = P.ngrp;
+    w.npc = P.npc;
+    w.pu = P.pu;
+    const long long grid = (long long)ctx->K * P.U;
+    if (grid > 0x7fffffffLL) return fail(ctx, PCL_ESHAPE, "pcl_eval / pcl_jac: %lld workgroups exceed the grid limit", grid);
+    const void *f = jac ? (const void *)pcl_var_large_exp_kernel<true> : (const void *)pcl_var_large_exp_kernel<false>;
+    if (int rc = var_set_lds(ctx, f, P.lds)) return rc;
+    void *args[] = {&p, &w};
+    HIP_TRY(ctx, hipLaunchKernel(f, dim3((unsigned)grid), dim3((unsigned)P.threads), args, P.lds, ctx->stream));
+    ctx->last_kernel = jac ? 370 : 371;  // the large variational exponential kernel: residual + Jacobian | residual only
+    ctx->last_n_stream = 0;
+    return PCL_OK;
+}
+
 static int var_launch_fused(pcl_ctx *ctx, const double *Z, double *delta, double *vals, bool compact = false) {
     ON_DEVICE(ctx);
+    if (ctx->large_var_exp) return var_large_exp_launch(ctx, Z, delta, vals);
     if (ctx->vexp) return var_exp_launch(ctx, Z, delta, vals, compact);
     if (ctx->desc.pade_order == 0)
         return fail(ctx, PCL_EINVAL, "pcl_eval / pcl_jac: the context was created with pade_order = 0; call pcl_set_order_policy (or a host-pointer entry point) first");

@@ -11,6 +11,7 @@
 //   pcl_kernel_var_large.hpp        ... the variational integrators there (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR): chain units of 1 + v components, panel units of the powers and, one variation at a time, the Frechet powers
 //   pcl_kernel_var_large_hess.hpp   ... ... their Hessian of the Lagrangian (option large_var_hess): the chains of pcl_kernel_pade_large_hess.hpp on the lifted generator, one pass per component
 //   pcl_kernel_var_large_rollout.hpp ... ... their rollout of the stacked state (option large_var_full): E and the Frechet derivatives L_i by column panels of one substepped Horner recurrence, then the chain of the knots
+//   pcl_kernel_var_large_exp.hpp    ... ... the exponential constraint on them (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP): that recurrence on the lifted pair in action form, the drive derivative carried through it
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
@@ -130,6 +131,8 @@ struct pcl_ctx {
     int *dvl_gtcol = nullptr;             // ... ... ... the transposed variation generators row-compressed, [v][n][vl_gtw] (allocated when the option is first set to 1)
     double *dvl_gtval = nullptr;
     int vl_gtw = 0, vl_etw = 0;           // ... ... ... the widths of those rows and of the transposed drive rows (dellt_*)
+    int large_var_exp = 0;                // ... ... PCL_LARGE_VAR_EXP with PCL_BATCH_VARIATIONAL_EXP (then `large_var` and `vexp` are set too): every residual / Jacobian launch is pcl_var_large_exp_kernel (pcl_kernel_var_large_exp.hpp); large_var_full serves the objective and the rollout, everything else is refused
+    int64_t opt_large_var_exp_drives = 0; // ... ... ... the most drives per chain unit of that launch (0 auto: the plan's count)
     int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
     int var_compact = 0;         // ... option var_compact: the compact Jacobian trio and the host expansion are served (either constraint kind)
     std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
@@ -431,11 +434,33 @@ extern "C" int pcl_create(const pcl_desc *dsc, pcl_ctx **out) {
     if (dsc->struct_size != (int32_t)sizeof(pcl_desc))
         return fail(nullptr, PCL_EINVAL, "pcl_create: desc.struct_size=%d, library expects %zu (ABI mismatch)",
                     dsc->struct_size, sizeof(pcl_desc));
-    // PCL_LARGE_N, PCL_LARGE_EXP and PCL_LARGE_VAR: stripped here, once; everything below (and the context) sees the plain batch mode
+    // PCL_LARGE_N, PCL_LARGE_EXP, PCL_LARGE_VAR and PCL_LARGE_VAR_EXP: stripped here, once; everything below (and the context) sees the plain batch mode
     const bool large_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_N) != 0;
     const bool large_exp_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_EXP) != 0;
     const bool large_var_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_VAR) != 0;
+    const bool large_var_exp_flag = dsc->batch_mode >= 0 && (dsc->batch_mode & PCL_LARGE_VAR_EXP) != 0;
     pcl_desc plain_desc = *dsc;
+    if (large_var_exp_flag) {
+        // the one valid combination: PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP with pade_order = PCL_ORDER_EXP
+        plain_desc.batch_mode &= ~(PCL_LARGE_N | PCL_LARGE_EXP | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP);
+        dsc = &plain_desc;
+        if (!large_flag || !large_var_flag)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP goes with %s (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, pade_order = PCL_ORDER_EXP)",
+                        !large_flag && !large_var_flag ? "PCL_LARGE_N and PCL_LARGE_VAR" : !large_flag ? "PCL_LARGE_N" : "PCL_LARGE_VAR");
+        if (dsc->batch_mode == PCL_BATCH_MEMBERS || dsc->batch_mode == PCL_BATCH_TRAJ)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP is the variational exponential constraint at generator dimensions 66 .. %d: it needs batch_mode PCL_BATCH_VARIATIONAL_EXP, not %s",
+                        PCL_LARGE_MAX_N, dsc->batch_mode == PCL_BATCH_MEMBERS ? "PCL_BATCH_MEMBERS" : "PCL_BATCH_TRAJ");
+        if (dsc->batch_mode == PCL_BATCH_VARIATIONAL)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP is the variational exponential constraint at generator dimensions 66 .. %d: it needs batch_mode PCL_BATCH_VARIATIONAL_EXP, not PCL_BATCH_VARIATIONAL (the Pade constraint takes PCL_LARGE_N | PCL_LARGE_VAR alone)",
+                        PCL_LARGE_MAX_N);
+        if (dsc->batch_mode != PCL_BATCH_VARIATIONAL_EXP)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP needs batch_mode PCL_BATCH_VARIATIONAL_EXP, not batch_mode %d", dsc->batch_mode);
+        if (dsc->pade_order != PCL_ORDER_EXP)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP is the exponential constraint: it needs pade_order = PCL_ORDER_EXP, not a Pade order (got %d)", dsc->pade_order);
+        if (large_exp_flag)
+            return fail(nullptr, PCL_EINVAL, "pcl_create: PCL_LARGE_VAR_EXP does not go with PCL_LARGE_EXP: that flag belongs to plain contexts (PCL_BATCH_MEMBERS or PCL_BATCH_TRAJ)");
+        return var_create(dsc, out, true, true);
+    }
     if (large_flag || large_exp_flag || large_var_flag) {
         plain_desc.batch_mode &= ~(PCL_LARGE_N | PCL_LARGE_EXP | PCL_LARGE_VAR);
         dsc = &plain_desc;

@@ -21,7 +21,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP, PclError
+from ._lib import PCL_BATCH_MEMBERS, PCL_BATCH_TRAJ, PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP, PCL_LARGE_VAR_EXP, PclError
 from .trajectory import STATE, TIMESTEP, NamedTrajectory
 
 __all__ = [
@@ -77,6 +77,11 @@ def _ptr(a):
 #                    66 .. 128 (option ``large_var_full``): ``Objective.bind``, ``rollout``, ``rollout_dev``, ``variational_rollout`` work.  The
 #                    compact Jacobian stays refused there.  At a dimension up to 64 it sets nothing (``var_full``, which
 #                    ``enable_objective_and_rollout`` switches on, is that context's option).
+# large_var_exp      beside ``large_generator=True`` with ``pade_order="exp"`` on a variational constructor: the fourth flag ``PCL_LARGE_VAR_EXP``, the
+#                    exact exponential constraint on the lifted generator at dimensions 66 .. 128 (``large_variational_exp`` on the context):
+#                    residual and exact Jacobian with the value order of ``pade_order="exp"`` at dimensions up to 62.  ``large_var_full`` is
+#                    allowed beside it (objective and rollout: the kernels of the Pade kind, the same bits); ``exp_hessian``, ``var_compact`` and
+#                    ``large_var_hessian`` are not.  At a dimension up to 64 the ordinary variational exponential context serves.
 # large_var_hessian  beside ``large_generator=True`` on a variational constructor (Pade constraint): the Hessian of the Lagrangian at dimensions
 #                    66 .. 128 (option ``large_var_hess``; values, order and structure are the variational context's at dimensions up to 64):
 #                    ``hess``, ``hess_dev``, ``hess_structure``, ``hessian_structure``, ``eval_hessian_of_lagrangian`` work.  At a dimension up to
@@ -105,16 +110,27 @@ def _ptr(a):
 # the context is of the kind `yields`, which has a switch of its own; `refuse`, question -> sentence, in the order the questions are asked.
 # ROW ORDER IS PRECEDENCE: _check_services raises the first sentence that applies (tests/golden/keyword_trace.json has every combination).
 # ---------------------------------------------------------------------------
-_Service = collections.namedtuple("_Service", "keyword refuse when flag option beside constraint family sizes at yields", defaults=("on",) + (None,) * 8)
+_Service = collections.namedtuple("_Service", "keyword refuse when flag option beside constraint family sizes at yields without", defaults=("on",) + (None,) * 9)
 _SERVICES = (
     _Service("large_generator", {}, flag="PCL_LARGE_N"),
-    _Service("large_variational", flag="PCL_LARGE_VAR", beside="large_generator", constraint="pade context", family="variational", refuse={
+    # (`without`: the keywords that must be off beside this one)
+    _Service("large_var_exp", flag="PCL_LARGE_VAR_EXP", beside="large_generator", constraint="exp", family="variational",
+             without=("exp_hessian", "var_compact", "large_var_hessian"), refuse={
+        "family": "large_var_exp=True is the flag PCL_LARGE_VAR_EXP of a variational context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator with large_generator=True, pade_order=\"exp\"): a plain context takes large_exp=True",
+        "beside": "large_var_exp=True is the exponential constraint of a variational context created with large_generator=True "
+                  "(the flags PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP): it needs that keyword",
+        "constraint": "large_var_exp=True is the variational exponential constraint at generator dimensions 66 .. 128: it needs pade_order=\"exp\" (got %(order)r)",
+        "without": "large_var_exp=True serves residual and Jacobian, and with large_var_full=True the objective and the rollout: the Hessian of the "
+                   "Lagrangian and the compact Jacobian are not implemented for a large variational exponential context (PCL_LARGE_VAR_EXP), "
+                   "so exp_hessian, var_compact and large_var_hessian stay off"}),
+    _Service("large_variational", flag="PCL_LARGE_VAR", beside="large_generator", constraint="pade context, or exp beside large_var_exp", family="variational", refuse={
         "constraint": "large_generator=True on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" "
                       "(PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts",
         "family": "large_variational=True is the flag PCL_LARGE_VAR of a variational context (VariationalUnitaryIntegrator / "
                   "VariationalKetIntegrator with large_generator=True): a plain context takes large_generator=True alone",
         "beside": "large_variational=True goes with large_generator=True (the flags PCL_LARGE_N | PCL_LARGE_VAR): it needs that keyword"}),
-    _Service("large_var_full", option="large_var_full", beside="large_generator", constraint="pade context", family="variational", at="large_variational", refuse={
+    _Service("large_var_full", option="large_var_full", beside="large_generator", constraint="pade context, or exp beside large_var_exp", family="variational", at="large_variational", refuse={
         "family": "large_var_full=True is the objective and the rollout of a large variational context (VariationalUnitaryIntegrator / "
                   "VariationalKetIntegrator with large_generator=True): a plain context takes large_full=True",
         "beside": "large_var_full=True is the objective and the rollout of a variational context created with large_generator=True: it needs that keyword",
@@ -189,10 +205,14 @@ def _check_services(batch_mode=PCL_BATCH_MEMBERS, pade_order=4, *, plain_integra
                            "no plain integrator": plain_integrator}[row.family]  # fmt: skip
             elif question == "beside":
                 refused = not keywords.get(row.beside, False)
+            elif question == "without":
+                refused = any(keywords.get(other, False) for other in row.without)
             else:
                 exp = _lib.order_code(pade_order) == _lib.PCL_ORDER_EXP
+                pade_context = exp or batch_mode == PCL_BATCH_VARIATIONAL_EXP
                 refused = {"exp": not exp, "pade": exp, "pade, or exp beside large_exp": exp and not keywords.get("large_exp", False),
-                           "pade context": exp or batch_mode == PCL_BATCH_VARIATIONAL_EXP}[row.constraint]  # fmt: skip
+                           "pade context": pade_context,
+                           "pade context, or exp beside large_var_exp": pade_context and not keywords.get("large_var_exp", False)}[row.constraint]  # fmt: skip
             if refused:
                 raise ValueError(sentence % dict(order=pade_order, value=value))
     value = keywords.get("exp_hessian", False)
@@ -205,11 +225,11 @@ class _PclContext:
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False, large_variational=False, large_var_full=False, large_var_hessian=False):  # fmt: skip
+                 large_exp_reduce=False, large_variational=False, large_var_full=False, large_var_hessian=False, large_var_exp=False):  # fmt: skip
         keywords = dict(exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact, large_generator=large_generator, large_hessian=large_hessian,
                         large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
                         large_exp_reduce=large_exp_reduce, large_variational=large_variational, large_var_full=large_var_full,
-                        large_var_hessian=large_var_hessian)  # fmt: skip
+                        large_var_hessian=large_var_hessian, large_var_exp=large_var_exp)  # fmt: skip
         keywords["exp_hessian"] = _check_services(batch_mode, pade_order, **keywords)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         self._L = _lib.load()
@@ -224,7 +244,7 @@ class _PclContext:
         xo = np.ascontiguousarray(np.asarray(x_offs, dtype=np.int32).reshape(-1))
         desc = _lib.pcl_desc(
             struct_size=ctypes.sizeof(_lib.pcl_desc), d=d, n_drives=m, N=N, z_dim=z_dim, u_off=u_off, dt_off=dt_off,
-            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0) | (_lib.PCL_LARGE_EXP if large_exp else 0) | (_lib.PCL_LARGE_VAR if large_variational else 0), pade_order=pade_order, device_id=device,
+            batch=batch, batch_mode=batch_mode | (_lib.PCL_LARGE_N if large_generator else 0) | (_lib.PCL_LARGE_EXP if large_exp else 0) | (_lib.PCL_LARGE_VAR if large_variational else 0) | (PCL_LARGE_VAR_EXP if large_var_exp else 0), pade_order=pade_order, device_id=device,
             index_base=index_base, per_member_G0=int(bool(per_member_G0)), state_cols=state_cols, global_dim=global_dim,
             G0=g0.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
             Gj=gj.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
@@ -248,6 +268,7 @@ class _PclContext:
         self.large = bool(large_generator) and n > 64
         self.large_exp = bool(large_exp) and self.large
         self.large_variational = bool(large_variational) and self.large
+        self.large_variational_exp = bool(large_var_exp) and self.large_variational
         # a variational context: x_dim is the stacked state; goals and forms speak of component 0, the rollout returns one stacked trajectory
         self.variational = batch_mode in _VARIATIONAL_MODES
         # one attribute per option keyword, named like it: it follows the library's option (set_option), and so do the sizes the option governs
@@ -743,19 +764,19 @@ class HipVariationalIntegrator:
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
     derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian`` switches them on.
 
-    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator``, ``large_var_full`` and ``large_var_hessian``: what each serves is
+    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator``, ``large_var_full``, ``large_var_hessian`` and ``large_var_exp``: what each serves is
     said once, above ``_SERVICES`` in this module.  The other large keywords are accepted and, switched on, refused in the table's words."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
-                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False, large_var_hessian=False):
+                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False, large_var_hessian=False, large_var_exp=False):
         pade_order = _lib.order_code(pade_order)
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         batch_mode = PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL
         exp_hessian = _check_services(batch_mode, pade_order, exp_hessian=exp_hessian, var_compact=var_compact, large_generator=large_generator,
                                       large_variational=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
                                       large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce,
-                                      large_var_full=large_var_full, large_var_hessian=large_var_hessian)  # fmt: skip
+                                      large_var_full=large_var_full, large_var_hessian=large_var_hessian, large_var_exp=large_var_exp)  # fmt: skip
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -787,7 +808,7 @@ class HipVariationalIntegrator:
             batch=len(names), batch_mode=batch_mode, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
             large_generator=bool(large_generator), large_variational=bool(large_generator), large_var_full=bool(large_var_full),
-            large_var_hessian=bool(large_var_hessian),
+            large_var_hessian=bool(large_var_hessian), large_var_exp=bool(large_var_exp),
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)

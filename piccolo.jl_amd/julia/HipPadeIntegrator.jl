@@ -230,6 +230,7 @@ end
 # merit entry points are served.  This glue has not been executed (there is no Julia on the build or test machines), as the rest of this file.
 const PCL_ORDER_EXP = -1
 const PCL_LARGE_N = 256     # (0x100) pcl_desc.batch_mode flag (keyword large_generator): generator dimensions 66 .. 128: residual and Jacobian, the Hessian of the Lagrangian with large_hessian = true, objective and rollout with large_full = true, compact Jacobian and reduce payload with large_reduce = true
+const PCL_LARGE_VAR_EXP = 2048  # (0x800) a fourth batch_mode flag (keyword large_var_exp of the variational integrators, beside large_generator and pade_order = :exp): PCL_BATCH_VARIATIONAL_EXP at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_var_full = true
 const PCL_LARGE_VAR = 1024  # (0x400) a third batch_mode flag beside PCL_LARGE_N (keyword large_generator of the variational integrators): PCL_BATCH_VARIATIONAL on the Pade constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout of the stacked state with large_var_full = true
 const PCL_LARGE_EXP = 512   # (0x200) a second batch_mode flag beside PCL_LARGE_N (keyword large_exp, with pade_order = :exp): the exponential constraint at generator dimensions 66 .. 128: residual and Jacobian, objective and rollout with large_full = true, the Hessian of the Lagrangian with large_exp_hessian = true, compact Jacobian and reduce payload with large_exp_reduce = true
 _order_code(p::Integer) = Int(p)
@@ -339,11 +340,15 @@ end
 #      of the Lagrangian at generator dimensions 66 .. 128, with the values, order and structure of the variational context at 64 and below
 #      (the structure is then filled as there).  At 64 and below it sets nothing (that context serves its Hessian always).
 #      (These keywords' glue has not been executed: no Julia on the development machines.)
+#      large_var_exp = true (with large_generator = true and pade_order = :exp only): the library's fourth flag PCL_LARGE_VAR_EXP -- the exact
+#      exponential constraint on the lifted generator at generator dimensions 66 .. 128: residual and Jacobian with the value order of
+#      pade_order = :exp at 62 and below; large_var_full = true is allowed beside it, exp_hessian, var_compact and large_var_hessian are not
+#      (ArgumentError).  At 64 and below the ordinary variational exponential context serves.  (Glue not executed, as the rest.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
                       var_compact::Bool = false, large_generator::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false,
                       large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false, large_var_full::Bool = false,
-                      large_var_hessian::Bool = false)
+                      large_var_hessian::Bool = false, large_var_exp::Bool = false)
     large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
@@ -352,11 +357,17 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     large_hessian && throw(ArgumentError("HipPadeIntegrator: large_hessian = true is not served on a variational integrator (the flag PCL_LARGE_N goes with the plain Pade constraint)"))
     pade_order = _order_code(pade_order)
     expo = pade_order == PCL_ORDER_EXP
-    (large_generator && expo) &&
+    (large_var_exp && !large_generator) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_exp = true is the exponential constraint of a variational context created with large_generator = true (the flags PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP): it needs that keyword"))
+    (large_var_exp && !expo) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_exp = true is the variational exponential constraint at generator dimensions 66 .. 128: it needs pade_order = :exp"))
+    (large_var_exp && (exp_hessian !== false || var_compact || large_var_hessian)) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_exp = true serves residual and Jacobian, and with large_var_full = true the objective and the rollout: the Hessian of the Lagrangian and the compact Jacobian are not implemented for a large variational exponential context (PCL_LARGE_VAR_EXP), so exp_hessian, var_compact and large_var_hessian stay off"))
+    (large_generator && expo && !large_var_exp) &&
         throw(ArgumentError("HipPadeIntegrator: large_generator = true on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large variational contexts"))
     (large_var_full && !large_generator) &&
         throw(ArgumentError("HipPadeIntegrator: large_var_full = true is the objective and the rollout of a variational context created with large_generator = true: it needs that keyword"))
-    (large_var_full && expo) &&
+    (large_var_full && expo && !large_var_exp) &&
         throw(ArgumentError("HipPadeIntegrator: large_var_full = true serves the diagonal Pade orders 2 .. 10: pade_order = :exp (PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts"))
     (large_var_hessian && !large_generator) &&
         throw(ArgumentError("HipPadeIntegrator: large_var_hessian = true is the Hessian of the Lagrangian of a variational context created with large_generator = true: it needs that keyword"))
@@ -381,7 +392,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     ctx = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve G0s Gjv x_offs begin
         desc = PclDesc(sizeof(PclDesc), size(G0, 1) ÷ 2, m, traj.N, traj.dim, traj.components[u][1] - 1, traj.components[traj.timestep][1] - 1,
-                       length(names), (expo ? 3 #= PCL_BATCH_VARIATIONAL_EXP =# : 2 #= PCL_BATCH_VARIATIONAL =#) | (large_generator ? PCL_LARGE_N | PCL_LARGE_VAR : 0), pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
+                       length(names), (expo ? 3 #= PCL_BATCH_VARIATIONAL_EXP =# : 2 #= PCL_BATCH_VARIATIONAL =#) | (large_generator ? PCL_LARGE_N | PCL_LARGE_VAR : 0) | (large_var_exp ? PCL_LARGE_VAR_EXP : 0), pade_order, device, 1 #= 1-based =#, 1 #= G0 = [G_drift; Gv_i] =#,
                        state_cols, traj.global_dim, pointer(G0s), pointer(Gjv), pointer(x_offs))
         rc = ccall((:pcl_create, LIB), Cint, (Ref{PclDesc}, Ref{Ptr{Cvoid}}), desc, ctx)
         rc == 0 || error("pcl_create: ", _lasterr(C_NULL))
