@@ -366,9 +366,22 @@ typedef enum pcl_status {
  * (host-pointer calls deliver full values), streams and sync, options, and by option "large_var_full" = 1 the objective family and
  * pcl_rollout[_dev] through the kernels of a large variational context (the same bits: neither depends on the constraint; the rollout then has
  * the discretisation of the rows).  pcl_set_order_policy / pcl_set_order_from_trajectory: PCL_EINVAL, as on every exponential context.
- * PCL_ENOTIMPL, each message naming PCL_LARGE_VAR_EXP: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64], the compact trio, the merit /
+ * PCL_ENOTIMPL, each message naming PCL_LARGE_VAR_EXP: pcl_hess[_dev], pcl_hess_nnz, pcl_hess_structure[_i64] (unless option
+ * "large_var_exp_hess" is on: below), the compact trio, the merit /
  * reduce / step entry points, the collective and the member window, pcl_infidelity_dev, and the options "large_var_hess", "var_compact",
  * "var_exp_hess", "var_full" and "exp_hess" = 1.  The other large options = 1 are PCL_EINVAL, as on every context that is not of their kind.
+ * Option "large_var_exp_hess" (0 by default, never on by itself; 1 on every other kind of context -- all four flags at n <= 64 included -- and
+ * any other value, PCL_EINVAL; readable everywhere, 0 there): at 1 such a context serves pcl_hess_nnz, pcl_hess_structure[_i64], pcl_hess and
+ * pcl_hess_dev with the values, order and structure of PCL_BATCH_VARIATIONAL_EXP with "var_exp_hess" at n <= 62 for the same pcl_desc:
+ * (m + 1)(m + 2) / 2 + x_dim' (m + 1) values per interval, [(u_i,u_j), j <= i | (dt,u_j) | (dt,dt) | (u_l, X'_k) | (dt, X'_k)] over the stacked,
+ * component-major state (pcl_kernel_var_large_exp_hess.hpp: the adjoint of the Jacobian's substepped recurrence on the lifted generator with the
+ * second derivative carried, one pass per component as workgroups of their own, the passes added in order by a second launch; DESIGN.md 4.30;
+ * "last_hess_kernel" 370).  Back at 0 the refusals return in the same words.  Its workspaces and the transposed row tables are allocated when
+ * the option is first set to 1 (PCL_ENOMEM when that fails) and freed by pcl_destroy.  "large_var_exp_hess_drives" caps the drives per group of
+ * that launch (0 auto; PCL_EINVAL when negative or off such a context), "cols_per_slice" its state columns; no atomics: every split, two
+ * launches and both pointer paths give the same bits.  With multipliers that are zero on the variations, the scalars and the vectors of
+ * component 0 equal, as numbers, those of a plain PCL_LARGE_N | PCL_LARGE_EXP context with "large_exp_hess" on the same drift and drives.
+ * h = 0 gives exact zeros in (u,u) and (u,X').  The other refusals above stay at either value.
  * Options: "cols_per_slice" caps the state columns per chain workgroup, "general_slices" sets the least number of panel workgroups,
  * "large_var_exp_drives" caps the drives per chain workgroup (0 auto; PCL_EINVAL when negative or off such a context); get_option
  * "large_variational_exp" reads 1, "large_variational" 1, "last_kernel" 370 after a residual + Jacobian launch and 371 after a residual-only

@@ -104,15 +104,17 @@ static void var_large_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, Larg
 }
 // option large_var_hess = 1: the workspace of the partial sums and the transposed row tables of the drives and of the variation generators
 // (allocated here, on first use, not by pcl_create; the tables come from the lifted host copies the order policy keeps)
-static int var_large_hess_alloc(pcl_ctx *ctx, void **buf, size_t bytes, const char *what) {
+static int var_large_hess_alloc(pcl_ctx *ctx, void **buf, size_t bytes, const char *what, const char *key = "large_var_hess") {
     const hipError_t e = hipMalloc(buf, std::max<size_t>(bytes, 8));
     if (e == hipSuccess) return PCL_OK;
     *buf = nullptr;
     (void)hipGetLastError();
-    return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "large_var_hess = 1: %s (%zu B): %s", what, bytes, hipGetErrorString(e));
+    return fail(ctx, e == hipErrorOutOfMemory ? PCL_ENOMEM : PCL_EHIP, "%s = 1: %s (%zu B): %s", key, what, bytes, hipGetErrorString(e));
 }
-static int var_large_hess_enable(pcl_ctx *ctx) {
-    if (ctx->dlhpart && ctx->dellt_col && ctx->dellt_val && ctx->dvl_gtcol && ctx->dvl_gtval) return PCL_OK;
+// The row-compressed transposes of the drives (dellt_*) and of the variation generators (dvl_gt*): the tables of both Hessian options of the
+// large variational kinds, large_var_hess and large_var_exp_hess (`key`: the one being set)
+static int var_large_hess_tables(pcl_ctx *ctx, const char *key) {
+    if (ctx->dellt_col && ctx->dellt_val && ctx->dvl_gtcol && ctx->dvl_gtval) return PCL_OK;
     ON_DEVICE(ctx);
     const int n = ctx->n, m = ctx->desc.n_drives, v = ctx->var, nl = ctx->var_nl;
     // rows of A^T = columns of A, entries in ascending row order, zero padded to the widest
@@ -149,13 +151,20 @@ static int var_large_hess_enable(pcl_ctx *ctx) {
                {(void **)&ctx->dvl_gtval, gval.data(), gval.size() * sizeof(double), "the transposed variation rows"}};
     for (const Up &u : ups) {
         if (*u.dst) continue;
-        TRY(var_large_hess_alloc(ctx, u.dst, u.bytes, u.what));
+        TRY(var_large_hess_alloc(ctx, u.dst, u.bytes, u.what, key));
         if (u.bytes) HIP_TRY(ctx, hipMemcpy(*u.dst, u.src, u.bytes, hipMemcpyHostToDevice));
     }
     ctx->vl_etw = etw;
     ctx->vl_gtw = gtw;
-    if (!ctx->dlhpart)
-        TRY(var_large_hess_alloc(ctx, (void **)&ctx->dlhpart, (size_t)ctx->K * ctx->cols * ((size_t)m * (m + 1) + 1) * sizeof(double), "the workspace of the partial sums"));
+    return PCL_OK;
+}
+static int var_large_hess_enable(pcl_ctx *ctx) {
+    TRY(var_large_hess_tables(ctx, "large_var_hess"));
+    if (!ctx->dlhpart) {
+        ON_DEVICE(ctx);
+        const size_t m = ctx->desc.n_drives;
+        TRY(var_large_hess_alloc(ctx, (void **)&ctx->dlhpart, (size_t)ctx->K * ctx->cols * (m * (m + 1) + 1) * sizeof(double), "the workspace of the partial sums"));
+    }
     return PCL_OK;
 }
 static int launch_var_large_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
@@ -300,6 +309,123 @@ static int launch_large_exp_hess(pcl_ctx *ctx, const double *Z, const double *mu
     hipLaunchKernelGGL(pcl_large_exp_hess_sum_kernel, dim3((unsigned)items), dim3(256), 0, ctx->stream, p);
     HIP_TRY(ctx, hipGetLastError());
     ctx->last_hess_kernel = 320;  // the large exponential Hessian kernel
+    return PCL_OK;
+}
+
+// Hessian of the Lagrangian of a large variational exponential context (pcl_kernel_var_large_exp_hess.hpp; option large_var_exp_hess).  The plan is
+// large_exp_hess_plan's on TWO-COMPONENT column counts: a unit of pass b >= 1 holds component 0 and component b, so per state column 2 Td columns on
+// the diagonal (Td = 1 + mg + mg (mg + 1) / 2), 2 To off it (To = 1 + 2 mg + mg^2); wherever there is more than one group the buffer is sized by
+// 2 nc To, one group by 2 nc Td, no drives by 4 nc ([X_0 | X_b | (Ghat X')_0 | (Ghat X')_b] behind the chain).  The units of pass 0 use half of
+// it.  Among the slice widths nc <= 16 (option cols_per_slice > 0: that width, or the widest that fits) and the group sizes (option
+// large_var_exp_hess_drives caps them; each evened over its groups) that fit, the plan with the fewest 16-column tile passes per interval and pass,
+//     sx (ngrp ceil(2 nc Td / 16) + ngrp (ngrp - 1) / 2 ceil(2 nc To / 16)),
+// is taken, on a tie the fewest units, then the wider slice and the larger group.  U = sx ngrp (ngrp + 1) / 2 units per interval and pass, 1 + v
+// passes.  The smallest unit needs 8 columns per buffer; n = 128 has 9, so nothing is refused for m <= 24, n <= 128.  Every split gives the same bits.
+static void var_large_exp_hess_plan(const pcl_ctx *ctx, int n, int cols, int m, LargeExpHessPlan &P) {
+    static_cast<LargeTile &>(P) = large_tile(ctx->max_lds, n, m);
+    P.NBW = P.NB / 3;
+    const int t_min = m == 0 ? 2 : (m == 1 ? 3 : 4);  // per component, the narrowest unit: no drives | one drive | two groups of one
+    const int nc_fit = std::max(1, P.NBW / (2 * t_min));
+    const int nc_hi = std::min(nc_fit, ctx->opt_cols_per_slice > 0 ? (int)std::min<int64_t>(ctx->opt_cols_per_slice, cols) : std::min(cols, 16));
+    const int nc_lo = ctx->opt_cols_per_slice > 0 ? nc_hi : 1;
+    const int mg_cap = m > 0 ? (ctx->opt_large_var_exp_hess_drives > 0 ? (int)std::min<int64_t>(ctx->opt_large_var_exp_hess_drives, m) : m) : 0;
+    long long best_p = -1, best_u = -1;
+    P.sx = cols, P.nc = 1, P.mg = m > 0 ? 1 : 0, P.ngrp = std::max(m, 1), P.W = 2 * t_min;
+    for (int nc0 = nc_hi; nc0 >= nc_lo; --nc0) {
+        int nc = nc0;
+        const int sx = even_split(cols, nc);  // even slices
+        for (int mg0 = mg_cap; mg0 >= (m > 0 ? 1 : 0); --mg0) {
+            int mg = mg0;
+            const int ngrp = m > 0 ? even_split(m, mg) : 1;  // even groups
+            const int Td = m > 0 ? 1 + mg + mg * (mg + 1) / 2 : 2, To = 1 + 2 * mg + mg * mg;
+            const int W = 2 * nc * (ngrp > 1 ? To : Td);
+            if (W > P.NBW) continue;
+            const long long npo = (long long)ngrp * (ngrp - 1) / 2;
+            const long long passes = sx * (ngrp * (long long)((2 * nc * (m > 0 ? Td : 1) + 15) / 16) + npo * ((2 * nc * To + 15) / 16)), units = sx * (ngrp + npo);
+            if (best_p < 0 || passes < best_p || (passes == best_p && units < best_u)) best_p = passes, best_u = units, P.sx = sx, P.nc = nc, P.mg = mg, P.ngrp = ngrp, P.W = W;
+            if (m == 0) break;
+        }
+    }
+    P.passes = best_p;
+    P.U = P.sx * (P.ngrp * (P.ngrp + 1) / 2);
+    P.lds = (size_t)(P.fixed + 3LL * P.LD * P.W) * sizeof(double);
+}
+// option large_var_exp_hess = 1: the transposed row tables (those of large_var_hess) and the two workspaces, allocated here, on first use
+static int var_large_exp_hess_enable(pcl_ctx *ctx) {
+    TRY(var_large_hess_tables(ctx, "large_var_exp_hess"));
+    ON_DEVICE(ctx);
+    const size_t m = ctx->desc.n_drives, v = ctx->var, nscal = (m + 1) * (m + 2) / 2;
+    if (!ctx->dvleh_part)
+        TRY(var_large_hess_alloc(ctx, (void **)&ctx->dvleh_part, (size_t)ctx->K * (1 + v) * ctx->cols * nscal * sizeof(double), "the workspace of the partial sums", "large_var_exp_hess"));
+    if (!ctx->dvleh_vec)
+        TRY(var_large_hess_alloc(ctx, (void **)&ctx->dvleh_vec, (size_t)ctx->K * v * (m + 1) * (size_t)ctx->var_xdc * sizeof(double), "the workspace of the passes' vectors", "large_var_exp_hess"));
+    return PCL_OK;
+}
+static int launch_var_large_exp_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *hess) {
+    if (!ctx->large_var_exp_hess || !ctx->dvleh_part || !ctx->dvleh_vec) return fail(ctx, PCL_EINVAL, "pcl_hess: option large_var_exp_hess is off");
+    const pcl_desc &D = ctx->desc;
+    const int n = ctx->n, m = D.n_drives, v = ctx->var;
+    LargeExpHessPlan P;
+    var_large_exp_hess_plan(ctx, n, ctx->cols, m, P);
+    if (P.lds > (size_t)ctx->max_lds)
+        return fail(ctx, PCL_ESHAPE, "the large variational exponential Hessian kernel needs %zu B of LDS (> %d) for n = %d, m = %d", P.lds, ctx->max_lds, n, m);
+    KParams p;
+    memset(&p, 0, sizeof p);
+    p.Z = Z;
+    p.mu = mu;
+    p.hess = hess;
+    p.hpart = ctx->dvleh_part;
+    p.G0 = ctx->dvar_tab;  // (build_G as var_large_exp_launch sets it up: the drift, and the drives on the union table)
+    p.upos = ctx->dupos;
+    p.ucoef = ctx->ducoef;
+    p.n_upos = ctx->n_upos;
+    p.ell_val = ctx->dell_val;
+    p.ell_col = ctx->dell_col;
+    p.ell_w = ctx->ell_w;
+    p.ellt_val = ctx->dellt_val;
+    p.ellt_col = ctx->dellt_col;
+    p.ellt_w = ctx->vl_etw;
+    p.x_off0 = -1;
+    p.hess_per = hess_per(ctx);
+    p.d = D.d;
+    p.n = n;
+    p.m = m;
+    p.K = ctx->K;
+    p.z_dim = D.z_dim;
+    p.u_off = D.u_off;
+    p.dt_off = D.dt_off;
+    p.batch = 1;
+    p.cols = ctx->cols;
+    p.nc = P.nc;
+    p.S = P.U;
+    p.LD = P.LD;
+    p.lds_doubles = (int)(P.lds / sizeof(double));
+    VarLargeExpHessParams w;
+    memset(&w, 0, sizeof w);
+    w.gv_val = ctx->dvl_gval;
+    w.gv_col = ctx->dvl_gcol;
+    w.gv_w = ctx->vl_gw;
+    w.gvt_val = ctx->dvl_gtval;
+    w.gvt_col = ctx->dvl_gtcol;
+    w.gvt_w = ctx->vl_gtw;
+    w.vpart = ctx->dvleh_vec;
+    w.v = v;
+    for (int b = 0; b <= v; ++b) w.xo[b] = ctx->x_offs[b];
+    w.sx = P.sx;
+    w.mg = P.mg;
+    w.ngrp = P.ngrp;
+    w.Wc = P.W;
+    const long long items = ctx->K, grid = items * (1 + v) * P.U;
+    if (int rc = check_grid(ctx, grid)) return rc;
+    if (int rc = var_set_lds(ctx, (const void *)pcl_var_large_exp_hess_kernel, P.lds)) return rc;
+    hipLaunchKernelGGL(pcl_var_large_exp_hess_kernel, dim3((unsigned)grid), dim3((unsigned)P.threads), P.lds, ctx->stream, p, w);
+    HIP_TRY(ctx, hipGetLastError());
+    // the sums: per interval one workgroup for the scalars and the first piece of the X_0 vectors, up to 63 more for the rest of them
+    const long long vec = (long long)(m + 1) * ctx->var_xdc;
+    const unsigned chunks = (unsigned)std::max<long long>(1, std::min<long long>(64, (vec + 255) / 256));
+    hipLaunchKernelGGL(pcl_var_large_exp_hess_sum_kernel, dim3((unsigned)items, chunks), dim3(256), 0, ctx->stream, p, w);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->last_hess_kernel = 370;  // the large variational exponential Hessian kernel
     return PCL_OK;
 }
 
@@ -668,6 +794,7 @@ static int launch_hess(pcl_ctx *ctx, const double *Z, const double *mu, double *
     ON_DEVICE(ctx);
     if (int rc = check_device_error(ctx, "pcl_hess")) return rc;
     TRY(require(ctx, FEAT_HESS, "pcl_hess"));
+    if (ctx->large_var_exp) return launch_var_large_exp_hess(ctx, Z, mu, hess);
     if (ctx->large_var) return launch_var_large_hess(ctx, Z, mu, hess);
     if (ctx->large_exp) return launch_large_exp_hess(ctx, Z, mu, hess);
     if (ctx->large) return launch_pade_large_hess(ctx, Z, mu, hess);

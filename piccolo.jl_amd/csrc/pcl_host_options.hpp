@@ -129,12 +129,15 @@ static const OptRow kOptions[] = {
     gate_row("large_reduce", GATE_LARGE_REDUCE),
     gate_row("large_var_full", GATE_LARGE_VAR_FULL),  // (0: also drops goal, weights, regularisers)
     gate_row("large_var_hess", GATE_LARGE_VAR_HESS),
+    gate_row("large_var_exp_hess", GATE_LARGE_VAR_EXP_HESS),
     // ... the most drives per group of the large launches (0 auto), and the rollout's stages for measurements (0 both launches | 1 the propagators only | 2 the chain only)
     opt_row("var_large_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_var_large_drives, 0, OPT_MAX, 0, 0,
             "%s must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)", &pcl_ctx::large_var),
     opt_row("large_var_hess_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_var_hess_drives, 0, OPT_MAX, 0, 0,
             "%s must be >= 0, on a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR, generator dimension above 64)", &pcl_ctx::large_var),
     opt_row("large_var_exp_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_var_exp_drives, 0, OPT_MAX, 0, 0,
+            "%s must be >= 0, on a large variational exponential context (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, generator dimension above 64)", &pcl_ctx::large_var_exp),
+    opt_row("large_var_exp_hess_drives", OPT_IN_RANGE_OR_FAIL, &pcl_ctx::opt_large_var_exp_hess_drives, 0, OPT_MAX, 0, 0,
             "%s must be >= 0, on a large variational exponential context (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, generator dimension above 64)", &pcl_ctx::large_var_exp),
     read_only("large_variational_exp", OPT_READ(c->large_var_exp)),  // 1: a large variational exponential context (the four flags at a generator dimension above 64)
     read_only("large_variational", OPT_READ(c->large_var)),  // 1: a large variational context (PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64)

@@ -23,13 +23,14 @@ enum Feature {
 
 // The gate options (OPTIONS.md): a context flag each, 0 by default.
 enum Gate { GATE_NONE, GATE_EXP_HESS, GATE_EXP_FULL, GATE_VAR_FULL, GATE_VAR_COMPACT, GATE_VAR_EXP_HESS, GATE_LARGE_HESS, GATE_LARGE_FULL, GATE_LARGE_REDUCE,
-            GATE_LARGE_EXP_HESS, GATE_LARGE_EXP_REDUCE, GATE_LARGE_VAR_FULL, GATE_LARGE_VAR_HESS, N_GATES };
+            GATE_LARGE_EXP_HESS, GATE_LARGE_EXP_REDUCE, GATE_LARGE_VAR_FULL, GATE_LARGE_VAR_HESS, GATE_LARGE_VAR_EXP_HESS, N_GATES };
 
 static int exp_hess_fits(const pcl_ctx *ctx, const char *who);
 static int var_exp_hess_enable(pcl_ctx *ctx);
 static int large_hess_enable(pcl_ctx *ctx);
 static int large_exp_hess_enable(pcl_ctx *ctx);
 static int var_large_hess_enable(pcl_ctx *ctx);
+static int var_large_exp_hess_enable(pcl_ctx *ctx);
 static int var_set_full(pcl_ctx *ctx, int64_t on);
 static int large_set_full(pcl_ctx *ctx, int64_t on);
 static int var_large_set_full(pcl_ctx *ctx, int64_t on);
@@ -65,6 +66,8 @@ static const GateInfo kGates[N_GATES] = {
      var_large_set_full},
     {&pcl_ctx::large_var_hess, KIND_BIT(KIND_LARGE_VAR_EXP), "%s = 1 needs a large variational context (PCL_BATCH_VARIATIONAL | PCL_LARGE_N | PCL_LARGE_VAR at a generator dimension above 64); every other context has its Hessian options of its own", FEAT_HESS,
      [](pcl_ctx *c, int64_t on) { return on ? var_large_hess_enable(c) : PCL_OK; }},
+    {&pcl_ctx::large_var_exp_hess, 0, "%s = 1 needs a large variational exponential context (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP, pade_order = PCL_ORDER_EXP, at a generator dimension above 64); every other context has its Hessian options of its own", FEAT_HESS,
+     [](pcl_ctx *c, int64_t on) { return on ? var_large_exp_hess_enable(c) : PCL_OK; }},
 };
 
 // One cell of the table: served always ({}), never (NEVER), or while every gate it names is on.  `words` replaces the kind's refusal sentence.
@@ -86,7 +89,7 @@ static const Cell kService[N_KINDS][N_FEATURES] = {
     /* LARGE     */ {{GATE_LARGE_HESS},                         {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE},     {GATE_LARGE_REDUCE, GATE_LARGE_FULL},     ALWAYS},
     /* LARGE_EXP */ {{GATE_LARGE_EXP_HESS},                     {GATE_LARGE_FULL},  {GATE_LARGE_FULL},  {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE}, {GATE_LARGE_EXP_REDUCE, GATE_LARGE_FULL}, ALWAYS},
     /* LARGE_VAR */ {{GATE_LARGE_VAR_HESS},                     {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
-    /* LARGE_VAR_EXP */ {NEVER,                                 {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
+    /* LARGE_VAR_EXP */ {{GATE_LARGE_VAR_EXP_HESS},             {GATE_LARGE_VAR_FULL}, NEVER,             NEVER,                   NEVER,                   NEVER,                                    NEVER},
 };
 
 static bool serves(const pcl_ctx *ctx, Feature f) {

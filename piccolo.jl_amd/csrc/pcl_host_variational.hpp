@@ -11,6 +11,7 @@
 #include "pcl_kernel_var_large_hess.hpp"
 #include "pcl_kernel_var_large_rollout.hpp"
 #include "pcl_kernel_var_large_exp.hpp"
+#include "pcl_kernel_var_large_exp_hess.hpp"
 
 // Values per interval: blocks (2 + 4 v) C n^2 (delta_0: -B+, B-; per variation: -B+, B-, -L+_i, L-_i), then the tails x_dim' (m + 1).
 // PCL_BATCH_VARIATIONAL_EXP: blocks (1 + 2 v) C n^2 (delta_0: -E; per variation: -E, -L_i), the identity's diagonal x_dim', the tails x_dim' (m + 1).

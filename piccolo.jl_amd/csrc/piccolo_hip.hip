@@ -12,6 +12,7 @@
 //   pcl_kernel_var_large_hess.hpp   ... ... their Hessian of the Lagrangian (option large_var_hess): the chains of pcl_kernel_pade_large_hess.hpp on the lifted generator, one pass per component
 //   pcl_kernel_var_large_rollout.hpp ... ... their rollout of the stacked state (option large_var_full): E and the Frechet derivatives L_i by column panels of one substepped Horner recurrence, then the chain of the knots
 //   pcl_kernel_var_large_exp.hpp    ... ... the exponential constraint on them (PCL_BATCH_VARIATIONAL_EXP | PCL_LARGE_N | PCL_LARGE_VAR | PCL_LARGE_VAR_EXP): that recurrence on the lifted pair in action form, the drive derivative carried through it
+//   pcl_kernel_var_large_exp_hess.hpp ... ... ... its Hessian of the Lagrangian (option large_var_exp_hess): the adjoint recurrence of pcl_kernel_large_exp_hess.hpp on the lifted generator, one pass per component as workgroups of their own, the passes added by a second launch
 //   pcl_kernel_large_exp.hpp        ... the exponential constraint there (PCL_LARGE_N | PCL_LARGE_EXP): the substepped Taylor polynomial in action form, the derivative carried through it
 //   pcl_kernel_large_rollout.hpp    ... their rollout (option large_full): substepped Taylor propagators by column panels, then the chain of the knots
 //   pcl_kernel_pade_large_hess.hpp  ... their Hessian of the Lagrangian (option large_hess): forward Horner chain, backward chains on G^T, per-column partial sums
@@ -133,6 +134,10 @@ struct pcl_ctx {
     int vl_gtw = 0, vl_etw = 0;           // ... ... ... the widths of those rows and of the transposed drive rows (dellt_*)
     int large_var_exp = 0;                // ... ... PCL_LARGE_VAR_EXP with PCL_BATCH_VARIATIONAL_EXP (then `large_var` and `vexp` are set too): every residual / Jacobian launch is pcl_var_large_exp_kernel (pcl_kernel_var_large_exp.hpp); large_var_full serves the objective and the rollout, everything else is refused
     int64_t opt_large_var_exp_drives = 0; // ... ... ... the most drives per chain unit of that launch (0 auto: the plan's count)
+    int large_var_exp_hess = 0;           // ... ... ... option large_var_exp_hess: its Hessian of the Lagrangian is served (pcl_kernel_var_large_exp_hess.hpp; its tables are dellt_* and dvl_gt*, its workspace the two below)
+    int64_t opt_large_var_exp_hess_drives = 0;  // ... ... ... ... the most drives per group of that launch (0 auto: the plan's count)
+    double *dvleh_part = nullptr;         // ... ... ... ... per (interval, pass, state column) the (m + 1)(m + 2) / 2 partial sums (allocated when the option is first set to 1)
+    double *dvleh_vec = nullptr;          // ... ... ... ... per (interval, pass b >= 1) what the pass adds to the (u_l, X_0) and (dt, X_0) vectors: (m + 1) n cols doubles
     int var_full = 0;            // ... option var_full: the objective and the rollout are served (pcl_host_robust.hpp)
     int var_compact = 0;         // ... option var_compact: the compact Jacobian trio and the host expansion are served (either constraint kind)
     std::vector<double> var_w;   // ... [w_0 | w_1 .. w_v]: the infidelity's weight and the sensitivity terms' coefficients
@@ -787,7 +792,7 @@ extern "C" void pcl_destroy(pcl_ctx *ctx) {
     void *ptrs[] = {ctx->dhcr, ctx->dhcf, ctx->dhcx, ctx->dhcc, ctx->dh4x, ctx->dh4c, ctx->dGjd, ctx->dG0, ctx->ducoef, ctx->dcsr_val, ctx->dcsc_val, ctx->dupos, ctx->dcsr_ptr, ctx->dcsr_col,
                     ctx->dcsc_ptr, ctx->dcsc_row, ctx->dxoffs, ctx->dZ, ctx->dmu, ctx->ddelta, ctx->dvals, ctx->dhess,
                     ctx->dumap, ctx->dell_col, ctx->dell_val, ctx->duell_l, ctx->duell_v, ctx->ddbg, ctx->dellt_col, ctx->dellt_val,
-                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart, ctx->dvl_gcol, ctx->dvl_gval, ctx->dvl_gtcol, ctx->dvl_gtval};
+                    ctx->dhpart, ctx->dhcnt, ctx->dug0, ctx->dexpm, ctx->dxout, ctx->dreduce, ctx->dvar_tab, ctx->dvar_ecol, ctx->dvar_eval, ctx->dexph, ctx->dvexph, ctx->dvexph_part, ctx->dvexph_tiles, ctx->dlhpart, ctx->dlehpart, ctx->dvl_gcol, ctx->dvl_gval, ctx->dvl_gtcol, ctx->dvl_gtval, ctx->dvleh_part, ctx->dvleh_vec};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (ctx->dgoal) (void)hipFree(ctx->dgoal);

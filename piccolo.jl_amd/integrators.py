@@ -81,7 +81,13 @@ def _ptr(a):
 #                    exact exponential constraint on the lifted generator at dimensions 66 .. 128 (``large_variational_exp`` on the context):
 #                    residual and exact Jacobian with the value order of ``pade_order="exp"`` at dimensions up to 62.  ``large_var_full`` is
 #                    allowed beside it (objective and rollout: the kernels of the Pade kind, the same bits); ``exp_hessian``, ``var_compact`` and
-#                    ``large_var_hessian`` are not.  At a dimension up to 64 the ordinary variational exponential context serves.
+#                    ``large_var_hessian`` are not (this kind's Hessian keyword is ``large_var_exp_hessian``, next).  At a dimension up to 64 the
+#                    ordinary variational exponential context serves.
+# large_var_exp_hessian  beside ``large_var_exp=True``: the Hessian of the Lagrangian of that constraint at dimensions 66 .. 128 (option
+#                    ``large_var_exp_hess``: the adjoint of the Jacobian's substepped recurrence on the lifted generator, one pass per component;
+#                    values, order and structure are ``exp_hessian``'s on a variational context at dimensions up to 62): ``hess``, ``hess_dev``,
+#                    ``hess_structure``, ``hessian_structure``, ``eval_hessian_of_lagrangian`` work.  At a dimension up to 64 it sets nothing
+#                    (``exp_hessian`` is that context's switch).
 # large_var_hessian  beside ``large_generator=True`` on a variational constructor (Pade constraint): the Hessian of the Lagrangian at dimensions
 #                    66 .. 128 (option ``large_var_hess``; values, order and structure are the variational context's at dimensions up to 64):
 #                    ``hess``, ``hess_dev``, ``hess_structure``, ``hessian_structure``, ``eval_hessian_of_lagrangian`` work.  At a dimension up to
@@ -124,6 +130,11 @@ _SERVICES = (
         "without": "large_var_exp=True serves residual and Jacobian, and with large_var_full=True the objective and the rollout: the Hessian of the "
                    "Lagrangian and the compact Jacobian are not implemented for a large variational exponential context (PCL_LARGE_VAR_EXP), "
                    "so exp_hessian, var_compact and large_var_hessian stay off"}),
+    _Service("large_var_exp_hessian", option="large_var_exp_hess", beside="large_var_exp", family="variational", sizes="hess", at="large_variational_exp", refuse={
+        "family": "large_var_exp_hessian=True is the Hessian of the Lagrangian of a large variational exponential context (VariationalUnitaryIntegrator / "
+                  "VariationalKetIntegrator with large_generator=True, large_var_exp=True, pade_order=\"exp\"): a plain context takes large_exp_hessian=True",
+        "beside": "large_var_exp_hessian=True is the Hessian of the Lagrangian of a variational context created with large_var_exp=True "
+                  "(large_generator=True, pade_order=\"exp\"): it needs that keyword"}),
     _Service("large_variational", flag="PCL_LARGE_VAR", beside="large_generator", constraint="pade context, or exp beside large_var_exp", family="variational", refuse={
         "constraint": "large_generator=True on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order=\"exp\" "
                       "(PCL_BATCH_VARIATIONAL_EXP) has no large variational contexts",
@@ -183,7 +194,7 @@ _SERVICES = (
 )
 _BY_OPTION = {row.option: row for row in _SERVICES if row.option}
 # the order in which a constructor switches the options on (the tile plan before the Hessian that reads it)
-_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "large_var_full", "large_var_hess", "var_compact")
+_OPTION_ORDER = ("var_exp_hess_tiles", "exp_hess", "large_hess", "large_exp_hess", "exp_full", "large_full", "large_reduce", "large_exp_reduce", "large_var_full", "large_var_hess", "large_var_exp_hess", "var_compact")
 _VARIATIONAL_MODES = (PCL_BATCH_VARIATIONAL, PCL_BATCH_VARIATIONAL_EXP)
 
 
@@ -225,11 +236,11 @@ class _PclContext:
     def __init__(self, *, d, m, N, z_dim, u_off, dt_off, x_offs, G0, Gj, batch, batch_mode, per_member_G0=False,
                  global_dim=0, device=0, index_base=0, pade_order=4, state_cols=0, exp_hessian=False, exp_full=False, var_compact=False,
                  large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False, large_exp_hessian=False,
-                 large_exp_reduce=False, large_variational=False, large_var_full=False, large_var_hessian=False, large_var_exp=False):  # fmt: skip
+                 large_exp_reduce=False, large_variational=False, large_var_full=False, large_var_hessian=False, large_var_exp=False, large_var_exp_hessian=False):  # fmt: skip
         keywords = dict(exp_hessian=exp_hessian, exp_full=exp_full, var_compact=var_compact, large_generator=large_generator, large_hessian=large_hessian,
                         large_full=large_full, large_reduce=large_reduce, large_exp=large_exp, large_exp_hessian=large_exp_hessian,
                         large_exp_reduce=large_exp_reduce, large_variational=large_variational, large_var_full=large_var_full,
-                        large_var_hessian=large_var_hessian, large_var_exp=large_var_exp)  # fmt: skip
+                        large_var_hessian=large_var_hessian, large_var_exp=large_var_exp, large_var_exp_hessian=large_var_exp_hessian)  # fmt: skip
         keywords["exp_hessian"] = _check_services(batch_mode, pade_order, **keywords)
         pade_order = _lib.order_code(pade_order)  # ("exp": the exponential constraint, PCL_ORDER_EXP)
         self._L = _lib.load()
@@ -764,19 +775,21 @@ class HipVariationalIntegrator:
     objective and rollout are served; ``hessian_structure`` / ``eval_hessian_of_lagrangian`` raise the library's message (third Frechet
     derivatives: solve with a quasi-Newton Hessian) unless ``exp_hessian`` switches them on.
 
-    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator``, ``large_var_full``, ``large_var_hessian`` and ``large_var_exp``: what each serves is
+    The service keywords ``exp_hessian`` (``False``, ``True`` or ``"workspace"``), ``var_compact``, ``large_generator``, ``large_var_full``, ``large_var_hessian``, ``large_var_exp`` and ``large_var_exp_hessian``: what each serves is
     said once, above ``_SERVICES`` in this module.  The other large keywords are accepted and, switched on, refused in the table's words."""
 
     def __init__(self, sys, traj, x_name, x_variations, u_name, Gv, *, ket, device=0, index_base=0, pade_order=0, order_tol=1e-10, exp_hessian=False,
                  var_compact=False, large_generator=False, large_hessian=False, large_full=False, large_reduce=False, large_exp=False,
-                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False, large_var_hessian=False, large_var_exp=False):
+                 large_exp_hessian=False, large_exp_reduce=False, large_var_full=False, large_var_hessian=False, large_var_exp=False,
+                 large_var_exp_hessian=False):
         pade_order = _lib.order_code(pade_order)
         self.exponential = pade_order == _lib.PCL_ORDER_EXP
         batch_mode = PCL_BATCH_VARIATIONAL_EXP if self.exponential else PCL_BATCH_VARIATIONAL
         exp_hessian = _check_services(batch_mode, pade_order, exp_hessian=exp_hessian, var_compact=var_compact, large_generator=large_generator,
                                       large_variational=large_generator, large_hessian=large_hessian, large_full=large_full, large_reduce=large_reduce,
                                       large_exp=large_exp, large_exp_hessian=large_exp_hessian, large_exp_reduce=large_exp_reduce,
-                                      large_var_full=large_var_full, large_var_hessian=large_var_hessian, large_var_exp=large_var_exp)  # fmt: skip
+                                      large_var_full=large_var_full, large_var_hessian=large_var_hessian, large_var_exp=large_var_exp,
+                                      large_var_exp_hessian=large_var_exp_hessian)  # fmt: skip
         x_variations = [x_variations] if isinstance(x_variations, str) else list(x_variations)
         names = [x_name] + x_variations
         n = 2 * sys.levels
@@ -808,7 +821,7 @@ class HipVariationalIntegrator:
             batch=len(names), batch_mode=batch_mode, per_member_G0=True, global_dim=traj.global_dim, device=device,
             index_base=index_base, pade_order=pade_order, state_cols=cols, exp_hessian=exp_hessian, var_compact=var_compact,
             large_generator=bool(large_generator), large_variational=bool(large_generator), large_var_full=bool(large_var_full),
-            large_var_hessian=bool(large_var_hessian), large_var_exp=bool(large_var_exp),
+            large_var_hessian=bool(large_var_hessian), large_var_exp=bool(large_var_exp), large_var_exp_hessian=bool(large_var_exp_hessian),
         )  # fmt: skip
         if pade_order == 0:
             _decide_order(self._ctx, traj, u_name, m, order_tol)

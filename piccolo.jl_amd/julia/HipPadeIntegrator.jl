@@ -344,11 +344,15 @@ end
 #      exponential constraint on the lifted generator at generator dimensions 66 .. 128: residual and Jacobian with the value order of
 #      pade_order = :exp at 62 and below; large_var_full = true is allowed beside it, exp_hessian, var_compact and large_var_hessian are not
 #      (ArgumentError).  At 64 and below the ordinary variational exponential context serves.  (Glue not executed, as the rest.)
+#      large_var_exp_hessian = true (with large_var_exp = true only): the library's option large_var_exp_hess -- the Hessian of the Lagrangian of
+#      that constraint at generator dimensions 66 .. 128, with the values, order and structure of pade_order = :exp with exp_hessian = true at
+#      62 and below (the structure is then filled as there).  At 64 and below it sets nothing (exp_hessian is that context's switch); never on
+#      by itself.  (Glue not executed, as the rest.)
 function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVector{Symbol}, u::Symbol, scales::Vector{Float64}, state_cols::Int;
                       device::Integer = 0, pade_order::Union{Integer, Symbol} = 0, order_tol::Float64 = 1e-10, exp_hessian::Union{Bool, Symbol} = false,
                       var_compact::Bool = false, large_generator::Bool = false, large_hessian::Bool = false, large_full::Bool = false, large_reduce::Bool = false,
                       large_exp::Bool = false, large_exp_hessian::Bool = false, large_exp_reduce::Bool = false, large_var_full::Bool = false,
-                      large_var_hessian::Bool = false, large_var_exp::Bool = false)
+                      large_var_hessian::Bool = false, large_var_exp::Bool = false, large_var_exp_hessian::Bool = false)
     large_exp_reduce && throw(ArgumentError("HipPadeIntegrator: large_exp_reduce = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context; var_compact is its option)"))
     large_exp_hessian && throw(ArgumentError("HipPadeIntegrator: large_exp_hessian = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
     large_exp && throw(ArgumentError("HipPadeIntegrator: large_exp = true is not served on a variational integrator (the flags PCL_LARGE_N and PCL_LARGE_EXP go with a plain context)"))
@@ -363,6 +367,8 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
         throw(ArgumentError("HipPadeIntegrator: large_var_exp = true is the variational exponential constraint at generator dimensions 66 .. 128: it needs pade_order = :exp"))
     (large_var_exp && (exp_hessian !== false || var_compact || large_var_hessian)) &&
         throw(ArgumentError("HipPadeIntegrator: large_var_exp = true serves residual and Jacobian, and with large_var_full = true the objective and the rollout: the Hessian of the Lagrangian and the compact Jacobian are not implemented for a large variational exponential context (PCL_LARGE_VAR_EXP), so exp_hessian, var_compact and large_var_hessian stay off"))
+    (large_var_exp_hessian && !large_var_exp) &&
+        throw(ArgumentError("HipPadeIntegrator: large_var_exp_hessian = true is the Hessian of the Lagrangian of a variational context created with large_var_exp = true (large_generator = true, pade_order = :exp): it needs that keyword"))
     (large_generator && expo && !large_var_exp) &&
         throw(ArgumentError("HipPadeIntegrator: large_generator = true on a variational integrator serves the diagonal Pade orders 2 .. 10: pade_order = :exp has no large variational contexts"))
     (large_var_full && !large_generator) &&
@@ -407,7 +413,9 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     large_var = large_generator && size(G0, 1) > 64                   # (a large variational context: the Hessian of the Lagrangian is refused without large_var_hessian)
     (large_var && large_var_full) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_full", 1))
     (large_var && large_var_hessian) && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_hess", 1))
-    ((expo && !exp_hessian) || (large_var && !large_var_hessian)) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
+    lve_hess = large_var && large_var_exp && large_var_exp_hessian    # (a large variational exponential context with its Hessian switched on)
+    lve_hess && check(c, ccall((:pcl_set_option, LIB), Cint, (Ptr{Cvoid}, Cstring, Int64), c, "large_var_exp_hess", 1))
+    (!lve_hess && ((expo && !exp_hessian) || (large_var && !large_var_hessian))) ? (hnnz[] = 0; per[] = 0) : check(c, ccall((:pcl_hess_nnz, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), c, hnnz, per))
     core = PclCore(c, 1, Int(xd[]), Int(nr[]), Int(nnz[]), Int(hnnz[]), Float64[], Float64[], Float64[], false, false, 0)
     finalizer(_destroy!, core)
     pade_order == 0 && _decide_order!(core, traj, u, m, order_tol)
@@ -416,7 +424,7 @@ function _variational(sys, traj::NamedTrajectory, x::Symbol, x_vars::AbstractVec
     jr = Vector{Int32}(undef, core.jac_per); jc = similar(jr)
     check(c, ccall((:pcl_jac_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, jr, jc))
     hr = Vector{Int32}(undef, core.hess_per); hc = similar(hr)
-    ((expo && !exp_hessian) || large_var) || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
+    (!lve_hess && ((expo && !exp_hessian) || large_var)) || check(c, ccall((:pcl_hess_structure, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), c, hr, hc))
     # (B.f is refused for the stacked state, see _f: fcore stays `nothing`)
     return HipPadeIntegrator(core, 1, x, names, u, core.x_dim, core.rows_per, jr, jc, hr, hc, Int(ncol[]), G0, Gj, state_cols, order, nothing)
 end
